@@ -64,6 +64,33 @@ def test_single_rank_output_has_no_ladder():
         assert k in d, k
 
 
+def test_dump_outputs_repeats_bit_for_bit(tmp_path):
+    """--dump-outputs writes one seeded step's results as float .npy files; inputs are seeded, so
+    two runs with the same arguments (one core, ATen kernels) give identical files, however
+    many steps were timed before."""
+    import numpy as np
+    runs = []
+    for name, steps in (("a", "2"), ("b", "3")):
+        out = tmp_path / name
+        rc, lines, err = _self(1, ["--steps", steps, "--dump-outputs", str(out)])
+        assert rc == 0, err[-3000:]
+        d = _one_json(lines, err)
+        assert d["steps"] == int(steps) and d["ms_per_step"] > 0
+        files = sorted(os.listdir(out))
+        assert files == ["classifier_bias.npy", "classifier_weight.npy", "loss.npy"], files
+        arrs = {f: np.load(out / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        w = arrs["classifier_weight.npy"]
+        assert w.dtype == np.float32 and w.shape == (10, 512) and np.isfinite(w).all()
+        assert arrs["classifier_bias.npy"].dtype == np.float32
+        assert arrs["classifier_bias.npy"].shape == (10,) and arrs["loss.npy"].dtype == np.float64
+        # first step from random init on 10 classes: the loss is near ln(10) = 2.30
+        assert 2.0 < arrs["loss.npy"][0] < 3.0, arrs["loss.npy"]
+        runs.append(arrs)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+
 def test_torchrun_clean_run_reports_one_successful_attempt():
     rc, lines, err = _torchrun(2)
     assert rc == 0, err[-3000:]

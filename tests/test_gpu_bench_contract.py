@@ -31,7 +31,8 @@ def _run_bench(*extra, steps=4, warmup=3):
 def test_bench_json_contract(native_ext):
     import bench
     # timed steps 10..19: the window the lr-0.1 numerics test characterises
-    r = _run_bench(steps=10, warmup=10)
+    # --full: the reference's timing window is measured too (a plain run leaves it out)
+    r = _run_bench("--full", steps=10, warmup=10)
     for k in ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"]:
         assert k in r, k
@@ -57,6 +58,36 @@ def test_bench_json_contract(native_ext):
     assert r["replicas_consistent"] is True
     # the reference's own timing window (iterations 1..39, host sync per iteration)
     assert r["avg_ms_iter_1_39"] > 0 and r["img_s_iter_1_39"] > 0
+
+
+def test_plain_run_dumps_outputs_and_skips_the_reference_window(native_ext, tmp_path):
+    """A plain run times its steps only (no reference window without --full); --dump-outputs
+    writes one seeded step of the timed path as float .npy files of at most 64 MB."""
+    import numpy as np
+    r = _run_bench("--dump-outputs", str(tmp_path / "out"), steps=3)  # the headline config
+    assert r["steps"] == 3 and r["ms_per_step"] > 0
+    assert r["avg_ms_iter_1_39"] is None and r["img_s_iter_1_39"] is None
+    arrs = {f: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(arrs) == ["classifier_bias.npy", "classifier_weight.npy", "loss.npy"]
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert arrs["classifier_weight.npy"].dtype == np.float32
+    assert arrs["classifier_weight.npy"].shape == (10, 512)
+    assert arrs["classifier_bias.npy"].dtype == np.float32
+    assert arrs["classifier_bias.npy"].shape == (10,)
+    assert arrs["loss.npy"].dtype == np.float64
+    for a in arrs.values():
+        assert np.isfinite(a).all()
+    # one SGD step from random init: the loss on 10 classes is near ln(10) = 2.30
+    assert np.abs(arrs["classifier_bias.npy"]).max() > 0
+    assert 2.0 < arrs["loss.npy"][0] < 3.0, arrs["loss.npy"]
+    # a second run, with other timed steps before the dumped one, repeats the files to within
+    # bf16 rounding (2^-8 of the array's largest magnitude: the compute precision of the step)
+    _run_bench("--dump-outputs", str(tmp_path / "out2"), steps=5)
+    for f, a in arrs.items():
+        b = np.load(tmp_path / "out2" / f)
+        d = float(np.abs(a.astype(np.float64) - b).max())
+        print(f, "max diff", d, "max", float(np.abs(a).max()))
+        assert d <= 2.0 ** -8 * float(np.abs(a).max()), (f, d)
 
 
 def test_bench_protocol_batch_split(native_ext):
