@@ -295,18 +295,19 @@ PYBIND11_MODULE(_native, m) {
      py::arg("ws"), py::arg("ws_elems"), py::arg("stream"), py::arg("bn") = py::none(),
      py::arg("bna") = py::none());
   // SGD in the backward (world 1): register a conv weight's gradient view with its update
-  // (p, momentum buffer, bf16 copy, lr, momentum, wd, grad_scale, nesterov); dw = 0 with
+  // (p, momentum buffer, bf16 copy, lr, momentum, wd, grad_scale, nesterov; sched = device
+  // learning-rate table used instead of lr, api.h LrSched); dw = 0 with
   // clear = 1 switches it off. sgd_fuse_taken: gradient views whose WGRAD finish applied it
   // since sgd_fuse_begin.
   m.def("sgd_fuse_register", [](uintptr_t dw, uintptr_t p, uintptr_t buf, uintptr_t wc, float lr,
                                 float momentum, float wd, float grad_scale, int nesterov,
-                                int clear) {
+                                int clear, uintptr_t sched) {
     ddp_amd::SgdFuse f{P<float>(p), P<float>(buf), P<unsigned short>(wc), lr, momentum, wd,
-                       grad_scale, nesterov};
+                       grad_scale, nesterov, P<const ddp_amd::LrSched>(sched)};
     ddp_sgd_fuse_register(P<float>(dw), dw ? &f : nullptr, clear);
   }, py::arg("dw"), py::arg("p") = 0, py::arg("buf") = 0, py::arg("wc") = 0, py::arg("lr") = 0.f,
      py::arg("momentum") = 0.f, py::arg("wd") = 0.f, py::arg("grad_scale") = 1.f,
-     py::arg("nesterov") = 0, py::arg("clear") = 0);
+     py::arg("nesterov") = 0, py::arg("clear") = 0, py::arg("sched") = 0);
   m.def("sgd_fuse_begin", []() { ddp_sgd_fuse_begin(); });
   m.def("sgd_fuse_taken", []() {
     std::vector<uintptr_t> v(256);
@@ -498,10 +499,12 @@ PYBIND11_MODULE(_native, m) {
   });
 
   m.def("sgd", [](uintptr_t p, uintptr_t g, uintptr_t buf, size_t n, float lr, float momentum,
-                  float wd, float grad_scale, int nesterov, uintptr_t st) {
+                  float wd, float grad_scale, int nesterov, uintptr_t st, uintptr_t sched) {
     check(ddp_sgd(P<float>(p), P<float>(g), P<float>(buf), n, lr, momentum, wd, grad_scale,
-                  nesterov, S(st)), "sgd");
-  });
+                  nesterov, P<const ddp_amd::LrSched>(sched), S(st)), "sgd");
+  }, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("n"), py::arg("lr"), py::arg("momentum"),
+     py::arg("wd"), py::arg("grad_scale"), py::arg("nesterov"), py::arg("stream"),
+     py::arg("sched") = 0);
   m.def("conv_options", [](int stages) { ddp_conv_options(stages); }, py::arg("stages") = 2);
   // measured tile/split table (mode 0 fwd, 1 dgrad, 2 wgrad; GEMM dims M, N, K; tile 0..3 =
   // 128x128, 128x64, 64x128, 64x64) and the forced-tile switch used by tools/conv_tune.py
@@ -539,17 +542,19 @@ PYBIND11_MODULE(_native, m) {
                        uintptr_t buf, float lr, float momentum, float wd, float grad_scale,
                        int nesterov, uintptr_t st, int zero_grad, uintptr_t counter, int delta,
                        uintptr_t skip, uintptr_t shadow, uintptr_t slot, uintptr_t done,
-                       uintptr_t signal) {
+                       uintptr_t signal, uintptr_t sched, int sched_advance) {
     check(ddp_sgd_pack(P<void>(items), n_items, P<long long>(descs), P<float>(p), P<float>(g),
                        P<float>(buf), lr, momentum, wd, grad_scale, nesterov, zero_grad,
                        P<int>(counter), delta, P<const unsigned>(skip), P<unsigned short>(shadow),
-                       P<float>(slot), P<unsigned>(done), P<unsigned>(signal), S(st)),
+                       P<float>(slot), P<unsigned>(done), P<unsigned>(signal),
+                       P<ddp_amd::LrSched>(sched), sched_advance, S(st)),
           "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
      py::arg("nesterov"), py::arg("stream"), py::arg("zero_grad") = 0, py::arg("counter") = 0,
      py::arg("delta") = 0, py::arg("skip") = 0, py::arg("shadow") = 0, py::arg("slot") = 0,
-     py::arg("done") = 0, py::arg("signal") = 0);
+     py::arg("done") = 0, py::arg("signal") = 0, py::arg("sched") = 0,
+     py::arg("sched_advance") = 0);
   // descs: list of (p, wc, wt, K, Cr, C, R, S, krsc) as in pack_conv_weights
   m.def("shard_tail", [](uintptr_t segs, int n_segs, uintptr_t src, uintptr_t dst,
                          std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int, int,
@@ -578,9 +583,12 @@ PYBIND11_MODULE(_native, m) {
     ddp_sgd_tile_dims(RS, &tk, &tc);
     return std::make_pair(tk, tc);
   });
-  m.def("counter_add", [](uintptr_t c, int delta, uintptr_t st) {
-    check(ddp_counter_add(P<int>(c), delta, S(st)), "counter_add");
-  });
+  // sched (api.h LrSched) with sched_mode 1: whole advance, 2: the staged step becomes current
+  m.def("counter_add", [](uintptr_t c, int delta, uintptr_t st, uintptr_t sched, int sched_mode) {
+    check(ddp_counter_add(P<int>(c), delta, P<ddp_amd::LrSched>(sched), sched_mode, S(st)),
+          "counter_add");
+  }, py::arg("c"), py::arg("delta"), py::arg("stream"), py::arg("sched") = 0,
+     py::arg("sched_mode") = 0);
 
   m.def("synth_generate", [](uintptr_t images, uintptr_t labels, int n, int pix_per_img,
                              unsigned int seed, int classes, uintptr_t st) {
@@ -590,8 +598,10 @@ PYBIND11_MODULE(_native, m) {
   m.def("augment", [](uintptr_t images, uintptr_t labels, uintptr_t indices, uintptr_t cursor,
                       int L, int B, int H, int W, int Cp, int pad, int flip, unsigned int seed,
                       unsigned int epoch, std::vector<float> mean, std::vector<float> std_,
-                      uintptr_t x, uintptr_t y, uintptr_t st, uintptr_t zero, size_t zero_n) {
+                      uintptr_t x, uintptr_t y, uintptr_t st, uintptr_t zero, size_t zero_n,
+                      uintptr_t sched) {
     ddp_amd::AugArgs a{};
+    a.sched = P<ddp_amd::LrSched>(sched);
     a.zero = P<float>(zero);
     a.zero_n = zero ? zero_n : 0;
     a.images = P<unsigned char>(images); a.labels = P<int>(labels); a.indices = P<int>(indices);
@@ -603,7 +613,8 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("images"), py::arg("labels"), py::arg("indices"), py::arg("cursor"), py::arg("L"),
      py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cp"), py::arg("pad"), py::arg("flip"),
      py::arg("seed"), py::arg("epoch"), py::arg("mean"), py::arg("std"), py::arg("x"),
-     py::arg("y"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0);
+     py::arg("y"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0,
+     py::arg("sched") = 0);
   m.def("nchw_to_nhwc", [](uintptr_t x, int N, int C, int H, int W, int Cp, uintptr_t out,
                            uintptr_t st) {
     check(ddp_nchw_to_nhwc(P<float>(x), N, C, H, W, Cp, P<void>(out), S(st)), "nchw_to_nhwc");

@@ -141,6 +141,31 @@ struct HeadBnIn {
   unsigned short* y;        // [B][F] pooled features (written)
 };
 
+// Learning-rate schedule in device memory (optim/sgd.py FusedSGD.set_schedule): a captured step
+// bakes every float kernel argument in, so a per-step learning rate has to be READ by the update
+// kernels. One allocation per run: 4 header words, then ``n`` fp32 learning rates (the table of
+// optim/schedule.py LRSchedule, the same fp32 values the CPU oracle uses). Every update site
+// takes an optional ``const LrSched*``: null = the immediate ``lr`` argument, else
+// lr = table[min(step, n - 1)] (common.h sched_lr / sched_lr_block).
+//
+// Advancing, exactly once per training step: the blocks of the launch that ends a step read
+// ``step`` themselves, so that launch must not write it (a late block would see the next step's
+// rate) and a grid-wide "last block done" ticket costs one contended atomic per block (measured:
+// +60 us on the 1036-block VGG-11 launch). Instead its block 0 only STAGES the advance,
+// ``next = step + 1``, a word no update kernel reads, and a launch that runs between that one and
+// the next step's first reader makes it current, ``step = next``: the next step's batch launch
+// (data.hip augment_kernel, AugArgs::sched — the first kernel of a captured or eager engine
+// step, so no extra dispatch), or a one-thread launch right behind the update where no such
+// launch follows (ddp_counter_add mode 2: plain optimizer use, the eager loops). ``next`` is
+// thus the number of steps taken; ``step == next`` except between those two launches.
+struct LrSched {
+  unsigned step;  // index of the step being computed: what the update kernels read
+  unsigned n;     // table entries (>= 1)
+  unsigned next;  // staged value of ``step`` for the following training step
+  unsigned pad;
+  // float lr[n] follows
+};
+
 // SGD in the backward (conv_igemm.hip wgrad_finish_krsc_body): the optimizer step of one conv
 // weight, applied by the WGRAD split-K finish that produces its complete gradient
 // (torch.optim.SGD, dampening 0: d = g * grad_scale + wd * p; buf = momentum * buf + d;
@@ -151,6 +176,7 @@ struct SgdFuse {
   unsigned short* wc;   // bf16 forward operand [K][R][S][C] (C >= Cr, pad channels untouched)
   float lr, momentum, wd, grad_scale;
   int nesterov;
+  const LrSched* sched;  // optional: the learning rate comes from the device table, not ``lr``
 };
 
 // VGG input block (conv_l0.hip): conv 3x3 (8 padded channels -> 64) + train-mode BN + ReLU +
@@ -197,6 +223,8 @@ struct AugArgs {
   long long* y;                 // [B]
   float* zero;                  // optional side job: zero this many floats (the next forward's
   size_t zero_n;                //   per-step accumulator scratch, ops/common.py StepScratch)
+  LrSched* sched;               // optional side job: the learning-rate schedule's staged step
+                                //   becomes current (LrSched: step = next) before this step's updates
 };
 
 }  // namespace ddp_amd
@@ -274,8 +302,9 @@ int ddp_linear_bwd(const float* dlogits, const void* x, const float* W, int B, i
 int ddp_softmax_ce(const void* logits, int logits_bf16, const long long* labels, int B, int J,
                    float* loss_sum, int* correct, void* dlogits, int dlogits_bf16,
                    hipStream_t st);
+// sched (optional, here and below): device learning-rate table used instead of ``lr``
 int ddp_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd,
-            float grad_scale, int nesterov, hipStream_t st);
+            float grad_scale, int nesterov, const ddp_amd::LrSched* sched, hipStream_t st);
 int ddp_conv_fwd_smallk(const ddp_amd::ConvGeom* g, const void* x, const void* wc,
                         const float* bias, void* y, float* stats, hipStream_t st);
 void ddp_conv_options(int stages);
@@ -316,18 +345,22 @@ void ddp_conv_dense2x2_set(int on);
 void ddp_conv_tune_clear();
 void ddp_conv_force_tile(int tile_plus_one, int stages);
 int ddp_pack_conv_weights(const ddp_amd::PackDesc* descs, int n, hipStream_t st);
+// ``sched``: learning rate from the device table; ``sched_advance`` = 1: this launch ends the
+// training step and stages the table's next step (LrSched::next = step + 1)
 int ddp_sgd_pack(const void* items, int n_items, const long long* descs, float* p, float* g,
                  float* buf, float lr, float momentum, float wd, float grad_scale, int nesterov,
                  int zero_grad, int* counter, int delta, const unsigned* skip,
                  unsigned short* shadow, float* slot, unsigned* done, unsigned* signal,
-                 hipStream_t st);
+                 ddp_amd::LrSched* sched, int sched_advance, hipStream_t st);
 // tail of a pipelined step with sharded buckets: gathered small-tensor slots -> fp32 arena,
 // re-pack of channel-padded conv operands, then release-increment ``signal`` (optim.hip)
 int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,
                    const ddp_amd::PackDesc* pack, int n_pack, unsigned* done, unsigned* signal,
                    const unsigned* skip, hipStream_t st);
 void ddp_sgd_tile_dims(int RS, int* TK, int* TC);
-int ddp_counter_add(int* c, int delta, hipStream_t st);
+// c += delta (c may be null); with ``sched``, mode 1: a whole advance (step = next = step + 1,
+// the step's only launch), mode 2: the staged step becomes current (step = next)
+int ddp_counter_add(int* c, int delta, ddp_amd::LrSched* sched, int sched_mode, hipStream_t st);
 int ddp_synth_generate(unsigned char* images, int* labels, int n, int pix_per_img,
                        unsigned int seed, int classes, hipStream_t st);
 int ddp_augment(const ddp_amd::AugArgs* a, hipStream_t st);

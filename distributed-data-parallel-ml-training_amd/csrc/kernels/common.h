@@ -68,6 +68,24 @@ __device__ __forceinline__ float sgd_update1(float p, float g, float& b, float l
   return __builtin_fmaf(-lr, d, p);
 }
 
+// Learning rate of the current step from the device schedule (api.h LrSched). The step word is
+// never written by a launch that reads it, only by launches stream-ordered between the end of
+// one step and the next step's first reader, so all readers of one step see the same value.
+__device__ __forceinline__ float sched_lr(const LrSched* s) {
+  const unsigned k = __hip_atomic_load(&s->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned n = s->n;
+  return reinterpret_cast<const float*>(s + 1)[k < n ? k : n - 1];
+}
+// ... read once per block: thread 0 loads, LDS broadcast, barrier. ``s`` must be uniform over
+// the block (a kernel argument); null keeps the immediate value and takes no barrier.
+__device__ __forceinline__ float sched_lr_block(const LrSched* s, float lr) {
+  if (!s) return lr;
+  __shared__ float s_lr;
+  if (threadIdx.x == 0) s_lr = sched_lr(s);
+  __syncthreads();
+  return s_lr;
+}
+
 // bf16 <-> fp32 bit conversions. round-to-nearest-even; NaN kept NaN.
 __device__ __forceinline__ float bf2f(unsigned short h) {
   return __uint_as_float(((unsigned int)h) << 16);

@@ -1037,6 +1037,12 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
     }
     return;
   }
+  // master-only SGD with a scheduled learning rate (api.h LrSched): resolved once per thread,
+  // outside the tile loops. A plain uniform-address load, not the LDS broadcast of the other
+  // update sites: this kernel's single LDS array is sized to its occupancy budget, and the step
+  // word cannot change while a backward runs (it advances in the launch that ends the step).
+  float sgd_lr = 0.f;
+  if (SGDM && MODE == MODE_WGRAD) sgd_lr = args.sgd.sched ? sched_lr(args.sgd.sched) : args.sgd.lr;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = col0 + wn * WTN + j * 16 + cq;
@@ -1069,10 +1075,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
           float4 pv = *reinterpret_cast<const float4*>(args.sgd.p + e);
           float4 bv = *reinterpret_cast<const float4*>(args.sgd.buf + e);
           const SgdFuse& h = args.sgd;
-          pv.x = sgd_update1(pv.x, v[0], bv.x, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          pv.y = sgd_update1(pv.y, v[1], bv.y, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          pv.z = sgd_update1(pv.z, v[2], bv.z, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          pv.w = sgd_update1(pv.w, v[3], bv.w, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv.x = sgd_update1(pv.x, v[0], bv.x, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv.y = sgd_update1(pv.y, v[1], bv.y, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv.z = sgd_update1(pv.z, v[2], bv.z, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv.w = sgd_update1(pv.w, v[3], bv.w, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
           *reinterpret_cast<float4*>(args.sgd.p + e) = pv;
           *reinterpret_cast<float4*>(args.sgd.buf + e) = bv;
         } else if (g.wkrsc && g.Creal == g.C) {
@@ -1881,8 +1887,9 @@ __global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* ws, int 
 // Split-K finish for WGRAD into a [K][R][S][Cr] gradient: the GEMM row IS the gradient row, so
 // this is a vectorised sum of the slabs — no transpose. blockIdx.y = group of kWgFinishGroupKrsc
 // slabs (fixed order inside a group); several groups combine with atomics.
-__device__ __forceinline__ float sgd_step1(float p, float g, float& b, const SgdFuse& h) {
-  return sgd_update1(p, g, b, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+__device__ __forceinline__ float sgd_step1(float p, float g, float& b, const SgdFuse& h,
+                                           float lr) {
+  return sgd_update1(p, g, b, lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
 }
 
 // With ``sg.p`` (SGD in the backward, api.h SgdFuse; single group only: the sum is the final
@@ -1899,6 +1906,9 @@ __device__ __forceinline__ void wgrad_finish_krsc_body(const float* __restrict__
   const int z0 = by * kWgFinishGroupKrsc, z1 = min(splits, z0 + kWgFinishGroupKrsc);
   const bool single = gy == 1;
   const bool opt = single && sg.p != nullptr;
+  // scheduled learning rate (api.h LrSched): read once per block before the reduction; both
+  // conditions are uniform over the block (kernel arguments and its grid)
+  const float lr = opt ? sched_lr_block(sg.sched, sg.lr) : sg.lr;
   for (size_t i = bx * (size_t)blockDim.x + threadIdx.x; i < n4;
        i += (size_t)gx * blockDim.x) {
     float4 v = reinterpret_cast<const float4*>(ws + z0 * slab)[i];
@@ -1917,10 +1927,10 @@ __device__ __forceinline__ void wgrad_finish_krsc_body(const float* __restrict__
       if (Creal == C) {
         float4 pv = reinterpret_cast<float4*>(sg.p)[i];
         float4 bv = reinterpret_cast<float4*>(sg.buf)[i];
-        pv.x = sgd_step1(pv.x, v.x, bv.x, sg);
-        pv.y = sgd_step1(pv.y, v.y, bv.y, sg);
-        pv.z = sgd_step1(pv.z, v.z, bv.z, sg);
-        pv.w = sgd_step1(pv.w, v.w, bv.w, sg);
+        pv.x = sgd_step1(pv.x, v.x, bv.x, sg, lr);
+        pv.y = sgd_step1(pv.y, v.y, bv.y, sg, lr);
+        pv.z = sgd_step1(pv.z, v.z, bv.z, sg, lr);
+        pv.w = sgd_step1(pv.w, v.w, bv.w, sg, lr);
         reinterpret_cast<float4*>(sg.p)[i] = pv;
         reinterpret_cast<float4*>(sg.buf)[i] = bv;
         uint2 pk;
@@ -1936,7 +1946,7 @@ __device__ __forceinline__ void wgrad_finish_krsc_body(const float* __restrict__
           if (c + t >= Creal) continue;
           const size_t mi = krs * Creal + c + t;
           float b = sg.buf[mi];
-          const float np = sgd_step1(sg.p[mi], vv[t], b, sg);
+          const float np = sgd_step1(sg.p[mi], vv[t], b, sg, lr);
           sg.p[mi] = np;
           sg.buf[mi] = b;
           sg.wc[e + t] = f2bf(np);

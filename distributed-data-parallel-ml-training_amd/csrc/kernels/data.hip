@@ -77,6 +77,12 @@ __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
     }
     if (pix == 0) a.y[b] = a.labels[idx];
   }
+  // side job: the learning-rate schedule's staged step becomes current (api.h LrSched; nothing
+  // reads ``step`` between the previous step's last update launch and this step's first one)
+  if (a.sched && blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned k = __hip_atomic_load(&a.sched->next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   // side job: clear the next forward's BN-statistics scratch (saves a fill launch per step)
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.zero_n; i += stride)
     a.zero[i] = 0.f;

@@ -19,7 +19,8 @@ namespace ddp_amd {
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                   float* __restrict__ buf, size_t n, float lr,
                                                   float momentum, float wd, float grad_scale,
-                                                  int nesterov) {
+                                                  int nesterov, const LrSched* sched) {
+  lr = sched_lr_block(sched, lr);
   const size_t n4 = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -121,6 +122,11 @@ struct SgdHyper {
   // "every parameter updated" flag without a separate signal launch
   unsigned* done;
   unsigned* signal;
+  // optional learning-rate schedule (api.h LrSched): every block reads this step's rate from the
+  // table instead of ``lr``; ``sched_advance``: this launch ends the training step — block 0
+  // stages the next step (``next``, read by no block here; a later launch makes it current)
+  LrSched* sched;
+  int sched_advance;
 };
 
 // Last-block-done hand-off: every block's writes are fenced, the block that takes the last
@@ -155,6 +161,13 @@ __device__ __forceinline__ void signal_flag(unsigned* done, unsigned* signal) {
   }
 }
 
+// Stage the schedule's next step (api.h LrSched), by one thread of the launch that ends the
+// step. A skipped update stages it too: the step still counts.
+__device__ __forceinline__ void sched_stage(LrSched* s) {
+  const unsigned k = __hip_atomic_load(&s->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&s->next, k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper& h) {
   return sgd_update1(p, g, b, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
 }
@@ -169,6 +182,8 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
                                                        float* __restrict__ g,
                                                        float* __restrict__ buf, SgdHyper h) {
   __shared__ float tile[kTileElems];
+  h.lr = sched_lr_block(h.sched, h.lr);
+  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
   sgd_pack_body(items, descs, p, g, buf, h, tile);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
@@ -391,8 +406,13 @@ __global__ __launch_bounds__(256) void shard_tail_kernel(TailArgs a) {
   else if (threadIdx.x == 0) __hip_atomic_store(a.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ void counter_add_kernel(int* c, int delta) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *c += delta;
+__global__ void counter_add_kernel(int* c, int delta, LrSched* sched, int sched_mode) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (c) *c += delta;
+  if (!sched) return;
+  if (sched_mode == 1) sched_stage(sched);
+  const unsigned k = __hip_atomic_load(&sched->next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace ddp_amd
@@ -400,12 +420,13 @@ __global__ void counter_add_kernel(int* c, int delta) {
 using namespace ddp_amd;
 
 extern "C" int ddp_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum,
-                       float wd, float grad_scale, int nesterov, hipStream_t st) {
+                       float wd, float grad_scale, int nesterov, const LrSched* sched,
+                       hipStream_t st) {
   size_t blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, buf, n, lr,
-                     momentum, wd, grad_scale, nesterov);
+                     momentum, wd, grad_scale, nesterov, sched);
   return (int)hipGetLastError();
 }
 
@@ -430,9 +451,10 @@ extern "C" int ddp_sgd_pack(const void* items, int n_items, const long long* des
                             float* g, float* buf, float lr, float momentum, float wd,
                             float grad_scale, int nesterov, int zero_grad, int* counter,
                             int delta, const unsigned* skip, unsigned short* shadow, float* slot,
-                            unsigned* done, unsigned* signal, hipStream_t st) {
+                            unsigned* done, unsigned* signal, LrSched* sched, int sched_advance,
+                            hipStream_t st) {
   SgdHyper h{lr, momentum, wd, grad_scale, nesterov, zero_grad, counter, delta, skip, shadow, slot,
-             done, signal};
+             done, signal, sched, sched && sched_advance ? 1 : 0};
   if (n_items <= 0) return 0;
   hipLaunchKernelGGL(sgd_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, descs,
                      p, g, buf, h);
@@ -458,7 +480,8 @@ extern "C" void ddp_sgd_tile_dims(int RS, int* TK, int* TC) {
   else { *TK = 8; *TC = 16; }
 }
 
-extern "C" int ddp_counter_add(int* c, int delta, hipStream_t st) {
-  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, st, c, delta);
+extern "C" int ddp_counter_add(int* c, int delta, LrSched* sched, int sched_mode,
+                               hipStream_t st) {
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, st, c, delta, sched, sched_mode);
   return (int)hipGetLastError();
 }

@@ -139,7 +139,7 @@ class DeviceLoader:
         n = math.ceil(self.idx.numel() / self.batch_size)
         return min(n, self.max_batches) if self.max_batches else n
 
-    def _launch(self, x, y, indices_ptr, L, B, cursor_ptr):
+    def _launch(self, x, y, indices_ptr, L, B, cursor_ptr, sched=0):
         from ..ops.common import native, stream_handle, step_scratch
         pad, flip = (4, 1) if self.train else (0, 0)
         # the augment launch also clears the per-step BN-statistics scratch that the next
@@ -149,7 +149,8 @@ class DeviceLoader:
         native().augment(self.images.data_ptr(), self.labels.data_ptr(), indices_ptr, cursor_ptr,
                          L, B, self.ds.height, self.ds.width, self.cpad, pad, flip,
                          self.ds.seed & 0xFFFFFFFF, self.epoch, CIFAR_MEAN, CIFAR_STD,
-                         x.data_ptr(), y.data_ptr(), stream_handle(), zero=zp, zero_n=zn)
+                         x.data_ptr(), y.data_ptr(), stream_handle(), zero=zp, zero_n=zn,
+                         **({"sched": sched} if sched else {}))
 
     def batch(self, start, B):
         """Materialise samples [start, start+B) of this rank's shard (new tensors)."""
@@ -176,15 +177,17 @@ class DeviceLoader:
             self._static = (x, y)
         return self._static
 
-    def fill(self, advance=True):
+    def fill(self, advance=True, lr_sched=0):
         """Write the next batch (cursor-addressed, wraps around the shard) into the static
         buffers and advance the device cursor. Safe to capture into a hipGraph.
         ``advance=False`` leaves the increment to the caller (engine/step.py folds it into the
-        optimizer launch: see ``cursor_advance``)."""
+        optimizer launch: see ``cursor_advance``). ``lr_sched``: device learning-rate schedule
+        (optim/sgd.py) whose step, staged by the previous step's optimizer launch, this launch
+        makes current — the batch launch is the first kernel of an engine step."""
         from ..ops.common import native, stream_handle
         x, y = self.static_batch()
         self._launch(x, y, self.idx.data_ptr(), self.idx.numel(), self.batch_size,
-                     self.cursor.data_ptr())
+                     self.cursor.data_ptr(), sched=lr_sched)
         if advance:
             native().counter_add(self.cursor.data_ptr(), 1, stream_handle())
         return x, y

@@ -20,6 +20,7 @@ from ..models import build
 from ..optim import FusedSGD
 from ..parallel import (DistributedDataParallel, STRATEGIES, destroy, init_distributed_setup,
                         make_communicator, test_distributed_setup)
+from ..utils.cli import lr_schedule_from_args
 from ..utils import MetricsSink, Watchdog, load_checkpoint, local_rank_of, parse_all, pick_device, \
     save_checkpoint, seed_everything
 from .trainer import CrossEntropyLoss, test_model, train_model, train_model_graph
@@ -60,7 +61,11 @@ def main(part, argv=None):
         model = DistributedDataParallel(model, comm, bucket_cap_mb=args.bucket_mb,
                                         first_bucket_cap_mb=args.first_bucket_mb,
                                         captured=captured)
-    optimizer = FusedSGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=0.0001)
+    # --lr / --lr-schedule ... (opt-in; default: the reference's constant 0.1, nothing attached)
+    lr, schedule = lr_schedule_from_args(args, len(train_loader))
+    optimizer = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=0.0001)
+    if schedule is not None:
+        optimizer.set_schedule(schedule)
     if args.resume:
         load_checkpoint(args.resume, model, optimizer)
     sync = None
@@ -83,7 +88,7 @@ def main(part, argv=None):
         # it back after the capture, so the epoch starts exactly where the eager loop would
         from .step import TrainStep, SegmentedDDPStep, default_cuts
         arena = model.arena if hasattr(model, "arena") else optimizer.arena
-        snap = (arena.data.clone(), optimizer.momentum_buffer.clone())
+        snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), optimizer.lr_step)
         split = [int(v) for v in os.environ.get("DDP_AMD_SEGMENTED",
                                                 default_cuts(args.model, batch_size)).split(",")
                  if int(v) > 0]
@@ -103,6 +108,7 @@ def main(part, argv=None):
         torch.cuda.synchronize()
         arena.data.copy_(snap[0])
         optimizer.momentum_buffer.copy_(snap[1])
+        optimizer.set_lr_step(snap[2])  # the warm-up / validation steps used no schedule entry
         optimizer.repack()
         train_loader.cursor.zero_()
         del snap

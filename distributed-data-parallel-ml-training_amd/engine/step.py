@@ -90,7 +90,7 @@ class TrainStep:
         if self.opt_in_bwd:
             self.optimizer.register_in_backward()
         with trace_range("data"):
-            x, y = self.loader.fill(advance=not self.fold_opt)
+            x, y = self.loader.fill(advance=not self.fold_opt, **self._lr_sched())
         with trace_range("forward"):
             if self.fused:
                 # classifier + loss + loss meter in one kernel (no logits tensor, no extra adds)
@@ -107,13 +107,22 @@ class TrainStep:
                 # the optimizer launch also clears the gradients for the next step and advances
                 # the data cursor: no zero_grad fill, no counter kernel
                 self.optimizer.step(zero_grad=True, counter=self.loader.cursor_advance(),
-                                    fused_taken=self.opt_in_bwd)
+                                    fused_taken=self.opt_in_bwd,
+                                    **({"lr_advance": "stage"} if self._lr_sched() else {}))
             else:
                 self.optimizer.step()
         if self.opt_in_bwd:
             self.optimizer.unregister_in_backward()
         if not self.fused:
             self.loss_sum.add_(loss.detach())
+
+    def _lr_sched(self):
+        """An attached learning-rate schedule advances without a dispatch of its own: the
+        optimizer launch that ends a step stages the next step (``lr_advance="stage"``) and
+        the following step's batch launch makes it current (data/loader.py fill)."""
+        ptr = self.optimizer._sched_ptr() if (self.fold_opt and
+                                              hasattr(self.optimizer, "_sched_ptr")) else 0
+        return {"lr_sched": ptr} if ptr else {}
 
     def warmup(self, steps):
         """Eager steps on a side stream (also the fallback execution path)."""
@@ -142,6 +151,10 @@ class TrainStep:
     def step(self):
         if self.graph is not None:
             self.graph.replay()
+            # a learning-rate schedule advances on the device inside the replay (optim/sgd.py
+            # set_schedule); the optimizer's host mirror of the step index follows here
+            if hasattr(self.optimizer, "count_step"):
+                self.optimizer.count_step()
         else:
             self._body()
 
@@ -150,6 +163,10 @@ class TrainStep:
         engine/trainer.py train_model_graph): forward, backward, gradient sync (DDP buckets via
         the wrapper's reducer; 2A/2B via ``sync``) and the optimizer, on the same stream as the
         replays. Gradients are clear on entry when the optimizer launch clears them."""
+        if self._lr_sched():
+            # no batch launch of the loader precedes this step: make the learning-rate step
+            # that the last replay staged current before the backward reads it
+            self.optimizer.commit_lr_step()
         if not self.fold_opt:
             self.optimizer.zero_grad()
         if self.opt_in_bwd:
@@ -407,7 +424,7 @@ class SegmentedDDPStep(TrainStep):
             self.ddp._sync_buffers()  # what DDP.forward would do (no-op without buffers / world 1)
         with self.ddp.no_sync():
             with trace_range("data"):
-                x, y = self.loader.fill(advance=False)
+                x, y = self.loader.fill(advance=False, **self._lr_sched())
             with trace_range("forward"):
                 loss, cuts = self.ddp.module.forward_loss_split(
                     x, y, self.split, acc=self.loss_sum, transient=True)
@@ -472,6 +489,7 @@ class SegmentedDDPStep(TrainStep):
                 with trace_range(f"shard16_update_bucket{j}"):
                     self.shard16.step(j, stream=cs, skip=self._fp(4),
                                       counter=self.loader.cursor_advance() if last else None,
+                                      lr_advance="stage" if last else False,
                                       standin=self._standin(cs) if self.comm_a is None else None)
             else:
                 with trace_range(f"sync_bucket{j}"):
@@ -479,7 +497,8 @@ class SegmentedDDPStep(TrainStep):
                 with trace_range(f"optimizer_bucket{j}"):
                     self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs,
                                         skip=self._fp(4),
-                                        counter=self.loader.cursor_advance() if last else None)
+                                        counter=self.loader.cursor_advance() if last else None,
+                                        lr_advance="stage" if last else False)
             if last:  # small-tensor unpack + operand re-pack + signal D, one launch
                 with trace_range("shard16_tail"):
                     self.shard16.tail(stream=cs, done=self._fp(5), signal=self._fp(1),
@@ -488,7 +507,8 @@ class SegmentedDDPStep(TrainStep):
         if self.zero is not None:
             with trace_range(f"zero_update_bucket{j}"):
                 self.zero.step(j, stream=cs, skip=self._fp(4),
-                               counter=self.loader.cursor_advance() if last else None)
+                               counter=self.loader.cursor_advance() if last else None,
+                               lr_advance="stage" if last else False)
             if last:
                 native().flag_signal(self._fp(1), cs.cuda_stream)
             return
@@ -498,10 +518,13 @@ class SegmentedDDPStep(TrainStep):
             # a timed-out wait (error word set) skips the update: never apply gradients whose
             # bucket was not averaged
             # the last bucket's update launch also signals D (last-block-done ticket in
-            # flags[5]): no separate signal launch on the critical comm stream
+            # flags[5]): no separate signal launch on the critical comm stream. It also stages
+            # the next step of an attached learning-rate schedule (lr_advance; the next step's
+            # batch launch, which waits for D, makes it current)
             self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs, skip=self._fp(4),
                                 counter=self.loader.cursor_advance() if last else None,
-                                signal=(self._fp(5), self._fp(1)) if last else None)
+                                signal=(self._fp(5), self._fp(1)) if last else None,
+                                lr_advance="stage" if last else False)
 
     def _segments(self):
         return [self._seg_first] + [(lambda j=j: self._seg(j)) for j in range(1, len(self.buckets))]
@@ -586,12 +609,13 @@ def profile_stage_times(ddp, optimizer, criterion, loader, n_stages, reps=4):
     ``reps`` times with timing events between its segment graphs (the comm stream still runs
     each bucket's SGD, as in the real step). Segment j of that step is stage n_stages-1-j;
     stage n_stages-1's time also holds the forward, the classifier head and the data step.
-    Parameters, momentum and the data cursor are rolled back afterwards (without collectives
-    the replicas' updates would differ), so training continues from the same state on every
-    rank. Returns a list of n_stages floats (us, median over reps). Feeds
+    Parameters, momentum, the data cursor and the learning-rate schedule's step are rolled back
+    afterwards (without collectives the replicas' updates would differ), so training continues
+    from the same state on every rank. Returns a list of n_stages floats (us, median over reps). Feeds
     parallel/cut_plan.plan_cuts."""
     arena = ddp.arena
     snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), loader.cursor.clone())
+    lr_step = getattr(optimizer, "lr_step", 0)  # the profiled steps must not use the schedule up
     # module buffers too (ResNet's BatchNorm running statistics): the profiling batches must
     # not leave extra updates behind
     bufs = [b for b in ddp.module.buffers()]
@@ -615,6 +639,8 @@ def profile_stage_times(ddp, optimizer, criterion, loader, n_stages, reps=4):
         arena.data.copy_(snap[0])
         optimizer.momentum_buffer.copy_(snap[1])
         loader.cursor.copy_(snap[2])
+        if hasattr(optimizer, "set_lr_step"):
+            optimizer.set_lr_step(lr_step)
         for b, v in zip(bufs, bsnap):
             b.copy_(v)
         arena.grad.zero_()

@@ -28,6 +28,14 @@ class CrossEntropyLoss(nn.Module):
         return nn.functional.cross_entropy(logits, target)
 
 
+def _scheduled_lr(optimizer):
+    """Extra metrics field of one iteration: the learning rate it runs with, only when a
+    schedule is attached (optim/sgd.py set_schedule; read from the host mirror, no sync)."""
+    if getattr(optimizer, "schedule", None) is None:
+        return {}
+    return {"lr": optimizer.current_lr()}
+
+
 def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", sync=None,
                 log=print, metrics=None, watchdog=None, rank=0):
     running_loss = 0.0
@@ -36,6 +44,7 @@ def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", 
     for batch_idx, (data, target) in enumerate(train_loader):
         fault_point(rank, batch_idx)
         start_time = time.perf_counter_ns()
+        lr = _scheduled_lr(optimizer)
         with trace_range("data"):
             data, target = data.to(device), target.to(device)
 
@@ -64,7 +73,7 @@ def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", 
             log(f'Total time for 1-39 iteration in ns: {total_time}')
             log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
         if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt)
+            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr)
         if watchdog is not None:
             watchdog.beat()
     stats["total_1_39_ns"] = total_time
@@ -91,6 +100,7 @@ def train_model_graph(step, train_loader, epoch, log=print, metrics=None, watchd
     for batch_idx in range(nb):
         fault_point(rank, batch_idx)
         start_time = time.perf_counter_ns()
+        lr = _scheduled_lr(step.optimizer)
         if batch_idx < nfull:
             step.step()
         else:
@@ -106,7 +116,7 @@ def train_model_graph(step, train_loader, epoch, log=print, metrics=None, watchd
             log(f'Total time for 1-39 iteration in ns: {total_time}')
             log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
         if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt)
+            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr)
         if watchdog is not None:
             watchdog.beat()
     if hasattr(step, "check_error"):

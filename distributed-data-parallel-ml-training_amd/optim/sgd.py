@@ -6,10 +6,19 @@ initialised to the first gradient. On the GPU one launch of ``sgd_kernel`` (csrc
 updates the whole flat parameter arena, followed by one launch that re-packs every conv weight
 into the bf16 MFMA operand layouts the next forward consumes. On the CPU it is exactly
 ``torch.optim.SGD`` (the oracle).
+
+Learning-rate schedules (``set_schedule``): a captured step bakes the ``lr`` kernel argument in,
+so with a schedule attached the fp32 table of optim/schedule.py lives in device memory
+(csrc/kernels/api.h LrSched), every update kernel reads this step's entry from it, and the
+table's step word advances once per training step: the launch that ends the step stages the
+next index and a later launch makes it current (the engine's next batch launch, or a one-thread
+launch right behind the update). On the CPU the same fp32 value is written to
+``param_groups[0]["lr"]`` before each step.
 """
 import torch
 
 from .arena import arena_for
+from .schedule import LRSchedule
 
 
 class FusedSGD(torch.optim.SGD):
@@ -31,6 +40,99 @@ class FusedSGD(torch.optim.SGD):
             # CPU: plain torch.optim.SGD; the flat arena (if the DDP wrapper built one) serves the
             # element-range update of the ZeRO-1 path (step_elements)
             self.arena = getattr(params[0], "_ddp_amd_arena", None) if params else None
+        self._schedule = None
+        self._lr_step = 0    # host mirror of the device step word: steps taken so far
+        self._lr_dev = None  # device LrSched: int32 [step, n, next, pad] + n fp32 rates
+
+    # ------------------------------------------------------------------ learning-rate schedule
+    def set_schedule(self, schedule, step=0):
+        """Attach an ``LRSchedule`` (``None`` detaches): from now on step k of the run uses
+        ``schedule.table()[min(k, total_steps - 1)]``, starting at k = ``step``. GPU: uploads the
+        table into the optimizer's device structure — allocated ONCE and reused, so its address
+        survives re-captures (a longer table than any before re-allocates it: capture after
+        attaching) — and sets its step word; the host keeps a mirror of the step index, counted
+        per ``step()`` / replay, so ``current_lr()`` needs no device sync."""
+        self._schedule = schedule
+        self._lr_step = int(step)
+        if schedule is None:
+            return
+        table = schedule.table()
+        if self._fused:
+            n = table.numel()
+            if self._lr_dev is None or self._lr_dev.numel() < 4 + n:
+                self._lr_dev = torch.zeros(4 + n, dtype=torch.int32, device=self.arena.data.device)
+            self._lr_dev[4:4 + n].view(torch.float32).copy_(table)
+            self._lr_dev[:4].copy_(torch.tensor([int(step), n, int(step), 0], dtype=torch.int32))
+
+    @property
+    def schedule(self):
+        return self._schedule
+
+    @property
+    def lr_step(self):
+        """Steps counted so far (host mirror; the index of the NEXT step's learning rate)."""
+        return self._lr_step
+
+    def set_lr_step(self, k):
+        """Move the schedule to step k: the device step word and its host mirror (state
+        rollbacks after warm-up / capture / validation steps, checkpoint restore)."""
+        self._lr_step = int(k)
+        if self._schedule is not None and self._fused:
+            self._lr_dev[0:3:2].fill_(int(k))  # step and next
+
+    def lr_step_device(self):
+        """Steps taken according to the device (LrSched::next; one device read: tests and
+        consistency checks)."""
+        return int(self._lr_dev[2].item()) if self._sched_ptr() else self._lr_step
+
+    def current_lr(self):
+        """Learning rate the next step uses (no device sync)."""
+        if self._schedule is None:
+            return float(self.param_groups[0]["lr"])
+        return self._schedule.lr_at(self._lr_step)
+
+    def count_step(self):
+        """Advance the host mirror by one training step. Called by every eager step and by the
+        owner of a captured graph after each replay; a launch that is only being captured runs
+        nothing on the device and is not counted."""
+        if self._schedule is None:
+            return
+        if self._fused and torch.cuda.is_current_stream_capturing():
+            return
+        self._lr_step += 1
+
+    def _sched_ptr(self):
+        return self._lr_dev.data_ptr() if (self._schedule is not None and self._fused) else 0
+
+    def _sched_kw(self, advance):
+        """Extra arguments of a native update launch: none without a schedule (the launch is
+        then exactly the unscheduled one)."""
+        ptr = self._sched_ptr()
+        return {"sched": ptr, "sched_advance": int(bool(advance))} if ptr else {}
+
+    def commit_lr_step(self, stream=None):
+        """Make a staged step current now (one-thread launch): for an eager step that follows
+        ``lr_advance="stage"`` steps without the loader's batch launch in between."""
+        if self._sched_ptr():
+            from ..ops.common import native, stream_handle
+            native().counter_add(0, 0, stream if stream is not None else stream_handle(),
+                                 sched=self._sched_ptr(), sched_mode=2)
+
+    def _sched_commit(self, advance, stream):
+        """After an update launch that staged the next step (``advance``): make it current with
+        a one-thread launch, unless the caller leaves that to the next step's batch launch
+        (``advance == "stage"``: data/loader.py fill(lr_sched=...), engine/step.py)."""
+        if advance and advance != "stage" and self._sched_ptr():
+            from ..ops.common import native
+            native().counter_add(0, 0, stream, sched=self._sched_ptr(), sched_mode=2)
+        if advance:
+            self.count_step()
+
+    def _cpu_lr(self):
+        """CPU: this step's fp32 table entry into the param group (what torch.optim.SGD reads)."""
+        if self._schedule is not None:
+            self.param_groups[0]["lr"] = self._schedule.lr_at(self._lr_step)
+        return float(self.param_groups[0]["lr"])
 
     def _packs(self):
         return [p._ddp_amd_pack() for p in self.arena.params if hasattr(p, "_ddp_amd_pack")]
@@ -56,6 +158,7 @@ class FusedSGD(torch.optim.SGD):
         self._bwd_index = {}
         base_g, base_p = a.grad.data_ptr(), a.data.data_ptr()
         base_b = self.momentum_buffer.data_ptr()
+        sched = {"sched": self._sched_ptr()} if self._sched_ptr() else {}
         for i, p in enumerate(a.params):
             if not hasattr(p, "_ddp_amd_pack"):
                 continue
@@ -65,7 +168,8 @@ class FusedSGD(torch.optim.SGD):
             dw = base_g + 4 * a.offsets[i]
             nat.sgd_fuse_register(dw, pp, base_b + 4 * a.offsets[i], wc, float(g["lr"]),
                                   float(g["momentum"]), float(g["weight_decay"]),
-                                  float(self._grad_scale_factor), int(bool(g["nesterov"])))
+                                  float(self._grad_scale_factor), int(bool(g["nesterov"])),
+                                  **sched)
             self._bwd_index[dw] = i
         nat.sgd_fuse_begin()
 
@@ -164,13 +268,19 @@ class FusedSGD(torch.optim.SGD):
         return t
 
     @torch.no_grad()
-    def step_elements(self, lo, hi, stream=None, zero_grad=False, counter=None, skip=None):
+    def step_elements(self, lo, hi, stream=None, zero_grad=False, counter=None, skip=None,
+                      lr_advance=True):
         """SGD (fp32 master + momentum only) on arena elements [lo, hi): one launch on the GPU,
-        torch.optim.SGD's exact per-element math on the flat slices on the CPU."""
+        torch.optim.SGD's exact per-element math on the flat slices on the CPU.
+        ``lr_advance=False``: not the training step's last update (an attached schedule stays
+        at this step for the launches that follow); ``"stage"``: as in ``step``."""
         g = self.param_groups[0]
         lr, m, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
         a = self.arena
         if not self._fused:
+            lr = self._cpu_lr()
+            if lr_advance:
+                self.count_step()
             p, gr = a.data[lo:hi], a.grad[lo:hi]
             d = gr.add(p, alpha=wd) if wd != 0 else gr
             if m != 0:
@@ -197,7 +307,8 @@ class FusedSGD(torch.optim.SGD):
                           zero_grad=int(bool(zero_grad)),
                           counter=int(counter[0]) if counter else 0,
                           delta=int(counter[1]) if counter else 0,
-                          skip=int(skip) if skip else 0)
+                          skip=int(skip) if skip else 0, **self._sched_kw(lr_advance))
+        self._sched_commit(lr_advance, s)
 
     def _descs_ptr(self):
         return self._work_table()[2].data_ptr()
@@ -218,7 +329,7 @@ class FusedSGD(torch.optim.SGD):
 
     @torch.no_grad()
     def step(self, closure=None, zero_grad=False, counter=None, skip=None, params=None,
-             stream=None, fused_taken=False, signal=None):
+             stream=None, fused_taken=False, signal=None, lr_advance=None):
         """One fused launch. ``params = (i0, i1)``: only parameters i0 <= i < i1 (arena order);
         ``stream``: launch on this torch stream instead of the current one. ``zero_grad=True`` also clears every gradient after its use (the
         next step then needs no zero_grad fill); ``counter=(int32 device ptr, delta)`` is
@@ -226,9 +337,19 @@ class FusedSGD(torch.optim.SGD):
         device pointer of a uint32 error word: the update is skipped when it is non-zero.
         ``fused_taken=True``: skip the parameters whose update the backward already applied
         (register_in_backward). ``signal = (ticket ptr, flag ptr)``: the launch's last block to
-        finish release-increments the uint32 flag (zeroed uint32 ticket)."""
+        finish release-increments the uint32 flag (zeroed uint32 ticket). ``lr_advance``: this
+        launch ends the training step, so an attached schedule moves on to the next step after
+        it (default: a whole-arena step does, a ``params`` range does not — the pipelined step
+        passes it for its last bucket). True: the launch stages the next step and a one-thread
+        launch behind it makes it current; ``"stage"``: the caller's next batch launch does that
+        (``DeviceLoader.fill(lr_sched=...)``: no extra dispatch in an engine step)."""
+        if lr_advance is None:
+            lr_advance = params is None
         if not self._fused:
+            self._cpu_lr()
             out = super().step(closure)
+            if lr_advance:
+                self.count_step()
             if zero_grad:
                 super().zero_grad(set_to_none=False)
             return out
@@ -241,8 +362,14 @@ class FusedSGD(torch.optim.SGD):
             pack_only = self._master_in_backward()
             exclude = self._fused_in_backward() | pack_only
         items, n_items, descs = self._work_table(params, exclude, pack_only)
+        sched = self._sched_kw(lr_advance)
         if n_items == 0:  # every tensor was updated in the backward: only the data cursor
-            if counter:
+            if sched.get("sched_advance"):
+                native().counter_add(int(counter[0]) if counter else 0,
+                                     int(counter[1]) if counter else 0, s,
+                                     sched=sched["sched"], sched_mode=1)
+                self.count_step()
+            elif counter:
                 native().counter_add(int(counter[0]), int(counter[1]), s)
             if signal:
                 native().flag_signal(int(signal[1]), s)
@@ -257,11 +384,14 @@ class FusedSGD(torch.optim.SGD):
                           delta=int(counter[1]) if counter else 0,
                           skip=int(skip) if skip else 0,
                           done=int(signal[0]) if signal else 0,
-                          signal=int(signal[1]) if signal else 0)
+                          signal=int(signal[1]) if signal else 0, **sched)
+        self._sched_commit(lr_advance, s)
         return None
 
     def state_dict(self):
         sd = super().state_dict()
+        if self._schedule is not None:  # plain ints / floats / lists: loads with weights_only
+            sd["lr_schedule"] = {"schedule": self._schedule.state_dict(), "step": self._lr_step}
         if self._fused:
             # expose the momentum buffers in torch.optim.SGD's per-parameter layout
             a = self.arena
@@ -270,8 +400,11 @@ class FusedSGD(torch.optim.SGD):
         return sd
 
     def load_state_dict(self, sd):
+        ls = sd.get("lr_schedule")
+        if ls is not None:
+            self.set_schedule(LRSchedule.from_state_dict(ls["schedule"]), step=int(ls["step"]))
         if not self._fused:
-            return super().load_state_dict(sd)
+            return super().load_state_dict({k: v for k, v in sd.items() if k != "lr_schedule"})
         a = self.arena
         st = sd.get("state", {})
         for i, p in enumerate(a.params):

@@ -78,9 +78,13 @@ class ShardedUpdate:
         dst[k:].view(self.world - extra, base).copy_(img[extra:, :base])
 
     @torch.no_grad()
-    def step(self, j, stream=None, counter=None, skip=None):
+    def step(self, j, stream=None, counter=None, skip=None, lr_advance=None):
+        """``lr_advance``: bucket j's update ends the training step (a learning-rate schedule
+        attached to the optimizer then moves on; default: the last bucket)."""
         from .comm import AVG
         (i0, i1), (lo, hi) = self.buckets[j]
+        if lr_advance is None:
+            lr_advance = j == len(self.buckets) - 1
         a = self.arena
         cuda = a.data.is_cuda
         ctx = torch.cuda.stream(stream) if (cuda and stream is not None) else _null()
@@ -89,14 +93,16 @@ class ShardedUpdate:
             s0, s1 = self.shard(j)
             if (hi - lo) % self.world == 0:
                 self.comm.reduce_scatter_inplace(g, AVG, stream=stream)
-                self.opt.step_elements(s0, s1, stream=stream, counter=counter, skip=skip)
+                self.opt.step_elements(s0, s1, stream=stream, counter=counter, skip=skip,
+                                       lr_advance=lr_advance)
                 self.comm.all_gather_inplace(p, stream=stream)
             else:  # uneven shards through the padded [w, per] staging image
                 gi, pi = self._image(0, j), self._image(1, j)
                 self._pack(g, gi, j)
                 self.comm.reduce_scatter_inplace(gi.view(-1), AVG, stream=stream)
                 a.grad[s0:s1].copy_(gi[self.rank, :s1 - s0])
-                self.opt.step_elements(s0, s1, stream=stream, counter=counter, skip=skip)
+                self.opt.step_elements(s0, s1, stream=stream, counter=counter, skip=skip,
+                                       lr_advance=lr_advance)
                 self._pack(p, pi, j)
                 self.comm.all_gather_inplace(pi.view(-1), stream=stream)
                 self._unpack(pi, p, j)
@@ -333,9 +339,10 @@ class ShardedBf16Update:
         self._tail = (torch.tensor(segs if segs else [[0, 0, 0, 0]], dtype=torch.int32,
                                    device=dev), len(segs), descs)
 
-    def step(self, j, stream=None, counter=None, skip=None, standin=None):
+    def step(self, j, stream=None, counter=None, skip=None, standin=None, lr_advance=False):
         """Bucket j's reduce-scatter, shard SGD, grouped all-gather and unpack (on ``stream``).
-        ``standin(kind, nbytes, ptr, n)``: replaces the collectives (emulated world)."""
+        ``standin(kind, nbytes, ptr, n)``: replaces the collectives (emulated world).
+        ``lr_advance``: this bucket's update ends the training step (optim/sgd.py step)."""
         if not self.cuda:
             return self._step_cpu(j)
         from ..ops.common import native, stream_handle
@@ -362,7 +369,8 @@ class ShardedBf16Update:
                      int(bool(g["nesterov"])), cs, zero_grad=1,
                      counter=int(counter[0]) if counter else 0,
                      delta=int(counter[1]) if counter else 0, skip=int(skip) if skip else 0,
-                     shadow=sp, slot=slot_row)
+                     shadow=sp, slot=slot_row, **opt._sched_kw(lr_advance))
+        opt._sched_commit(lr_advance, cs)
         if standin is not None:
             standin("all_gather", 2 * (hi - lo) + 4 * self.world * plan["M"], slot_all, 0)
         else:
@@ -415,7 +423,9 @@ class ShardedBf16Update:
         plan = self._plan[j]
         s0, s1 = self.shard(j)
         a, g = self.arena, self.opt.param_groups[0]
-        lr, m, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
+        lr, m, wd = self.opt._cpu_lr(), float(g["momentum"]), float(g["weight_decay"])
+        if j == max(self.which):  # the step's last sharded bucket: the schedule moves on
+            self.opt.count_step()
         nesterov, gs = bool(g["nesterov"]), float(self.opt._grad_scale_factor)
         self.comm.reduce_scatter_inplace(a.grad[lo:hi], AVG)
         # the GPU launch's per-element math (common.h sgd_update1 = torch.optim.SGD's, momentum

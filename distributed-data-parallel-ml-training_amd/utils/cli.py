@@ -59,7 +59,40 @@ def build_parser(description=None, distributed=True):
                         'without a finished iteration (0 = off)')
     g.add_argument('--graph', action='store_true',
                    help='GPU: run each iteration as one replay of the captured training step')
+    g.add_argument('--lr', type=float, default=0.1, help='base learning rate (reference: 0.1)')
+    g.add_argument('--lr-schedule', default=None, choices=['constant', 'cosine', 'linear', 'step'],
+                   help='per-step learning-rate schedule over epochs x steps-per-epoch steps '
+                        '(works inside the captured step of --graph); default: none, constant --lr')
+    g.add_argument('--warmup-steps', type=int, default=0,
+                   help='linear warm-up from 0 to the base rate over this many steps')
+    g.add_argument('--lr-milestones', type=_int_list, default=[],
+                   help="--lr-schedule step: comma-separated global steps at which the rate is "
+                        "multiplied by --lr-gamma")
+    g.add_argument('--lr-gamma', type=float, default=0.1)
+    g.add_argument('--min-lr', type=float, default=0.0, help='end value of cosine / linear')
+    g.add_argument('--lr-ref-batch', type=int, default=None,
+                   help='linear scaling rule: lr *= global batch / this batch')
     return p
+
+
+def lr_schedule_from_args(args, steps_per_epoch):
+    """(base lr, LRSchedule | None) of a run: the linear scaling rule applied to --lr, and a
+    schedule over epochs x steps_per_epoch steps (the partial last batch of an epoch is a step)
+    only when --lr-schedule or --warmup-steps asks for one."""
+    lr = float(args.lr)
+    if args.lr_ref_batch:
+        lr *= args.global_batch / float(args.lr_ref_batch)
+    if args.lr_schedule is None and not args.warmup_steps:
+        return lr, None
+    from ..optim.schedule import LRSchedule
+    total = max(1, int(args.epochs) * int(steps_per_epoch))
+    return lr, LRSchedule(lr, total, warmup_steps=min(int(args.warmup_steps), total),
+                          decay=args.lr_schedule or "constant", milestones=args.lr_milestones,
+                          gamma=args.lr_gamma, min_lr=args.min_lr)
+
+
+def _int_list(v):
+    return [int(x) for x in str(v).split(",") if x.strip()]
 
 
 def finalize_args(args):
