@@ -187,7 +187,10 @@ PYBIND11_MODULE(_native, m) {
   });
   m.def("l0_bwd", [](py::tuple g, uintptr_t x, uintptr_t wc, uintptr_t bias, float eps, int relu,
                      uintptr_t coef, uintptr_t dy, uintptr_t sums, uintptr_t dz, uintptr_t dgamma,
-                     uintptr_t dbeta, uintptr_t code, uintptr_t zw, uintptr_t st, int sums_ready) {
+                     uintptr_t dbeta, uintptr_t code, uintptr_t zw, uintptr_t st, int sums_ready,
+                     uintptr_t dw, uintptr_t ws, size_t ws_elems) {
+    // dz = 0 with dw / ws: the weight gradient fused into the dz pass (dz never stored).
+    // Returns 1 when that form does not serve the call (nothing launched), else 0.
     auto c = geom(g);
     ddp_amd::L0Io io{};
     io.x = P<void>(x); io.wc = P<void>(wc); io.bias = P<float>(bias); io.eps = eps; io.relu = relu;
@@ -195,11 +198,15 @@ PYBIND11_MODULE(_native, m) {
     io.dgamma = P<float>(dgamma); io.dbeta = P<float>(dbeta); io.code = P<void>(code);
     io.zw = P<void>(zw);
     io.sums_ready = sums_ready;
-    check(ddp_l0_bwd(&c, &io, S(st)), "l0_bwd");
+    io.dw = P<float>(dw); io.ws = P<float>(ws); io.ws_elems = ws_elems;
+    const int rc = ddp_l0_bwd(&c, &io, S(st));
+    if (rc == -2) return 1;
+    check(rc, "l0_bwd");
+    return 0;
   }, py::arg("g"), py::arg("x"), py::arg("wc"), py::arg("bias"), py::arg("eps"), py::arg("relu"),
      py::arg("coef"), py::arg("dy"), py::arg("sums"), py::arg("dz"), py::arg("dgamma"),
      py::arg("dbeta"), py::arg("code"), py::arg("zw"), py::arg("stream"),
-     py::arg("sums_ready") = 0);
+     py::arg("sums_ready") = 0, py::arg("dw") = 0, py::arg("ws") = 0, py::arg("ws_elems") = 0);
   m.def("conv_tr_would_serve", [](py::tuple g, size_t ws_elems, int in_mode) {
     auto c = geom(g);
     return ddp_conv_tr_would_serve(&c, ws_elems, in_mode) == 1;

@@ -201,6 +201,10 @@ struct L0Io {
   float* dbeta;
   int sums_ready;       // backward: ``sums`` already accumulated (the next block's dgrad finish,
                         // BnBwdFuse::code) -> the dz pass only
+  // backward with the weight gradient fused into the dz pass (``dz`` null): dz is never stored
+  float* dw;            // fp32 gradient [64][Cr][3][3] or [64][3][3][Cr] (ConvGeom::wkrsc), added to
+  float* ws;            // split-K slabs: one compact [64][28] fp32 partial per block
+  size_t ws_elems;      // (ddp_l0_bwd returns 1 and launches nothing when it is too small)
 };
 
 struct PackDesc {
@@ -320,6 +324,9 @@ int ddp_l0_bwd(const ddp_amd::ConvGeom* g, const ddp_amd::L0Io* io, hipStream_t 
 int ddp_conv_wgrad_final(const ddp_amd::ConvGeom* g, const void* dy, const void* x, float* dw,
                          float* ws, size_t ws_elems, int splits, hipStream_t st);
 int ddp_sgd_fuse_taken(uintptr_t* out, int cap);
+// a complete gradient produced outside conv_igemm.hip by a layer without a DGRAD (conv_l0.hip's
+// fused weight gradient): the registered step for ``dw`` (1, marked taken) or none (0)
+int ddp_sgd_fuse_take_final(const float* dw, ddp_amd::SgdFuse* out);
 // gradient views whose MASTER a pair's unsplit WGRAD epilogue updated (operand re-pack pending)
 int ddp_sgd_fuse_taken_master(uintptr_t* out, int cap);
 // sweeps (tools/conv_tune.py --pairs): force the paired launch with these split-K factors (0 = off)

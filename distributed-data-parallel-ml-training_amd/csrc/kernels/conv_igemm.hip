@@ -3095,6 +3095,12 @@ extern "C" int ddp_conv_wgrad_final(const ConvGeom* g, const void* dy, const voi
   g_sgd_allow = false;
   return r;
 }
+extern "C" int ddp_sgd_fuse_take_final(const float* dw, SgdFuse* out) {
+  g_sgd_allow = true;
+  *out = sgd_fuse_for(dw, 1);
+  g_sgd_allow = false;
+  return out->p != nullptr;
+}
 extern "C" int ddp_sgd_fuse_taken(uintptr_t* out, int cap) {
   int n = 0;
   for (const float* p : g_sgd_taken) {

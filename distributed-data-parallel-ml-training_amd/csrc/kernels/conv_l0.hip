@@ -14,9 +14,20 @@
 //   l0_fwd_kernel    conv -> BN (coefficients folded from the statistics in every block; block 0
 //                    writes the [6][64] table) -> ReLU -> 2x2 max-pool -> pooled y (8.4 MB) and,
 //                    per pooled value, the window position its gradient goes to (1 B, 4.2 MB)
-//   l0_bwd_kernel<0> conv -> BN-backward sums S1 / S2 of the routed gradient
-//   l0_bwd_kernel<1> conv -> dz = scale * (dy_bn - k1 - xhat * k2) stored bf16 for the weight
-//                    gradient GEMM (k1 / k2 folded from S1 / S2; block 0 adds dgamma / dbeta)
+//   l0_sums_kernel   BN-backward sums S1 / S2 of the routed gradient from dy, code and the
+//                    recorded winner z (no conv; or taken by the next block's dgrad finish)
+//   l0_bwd_kernel<2> conv -> dz = scale * (dy_bn - k1 - xhat * k2) rounded to bf16 (k1 / k2
+//                    folded from S1 / S2; block 0 adds dgamma / dbeta) -> weight gradient
+//                    dW[k][tap][c] += sum over the tile's pixels of dz * x, MFMA into fp32
+//                    accumulators that live across the wave's tiles -> one compact [64][28]
+//                    fp32 partial per block. dz, the layer's last full-resolution tensor
+//                    (33.5 MB at b256), is never stored: its only consumer was the weight
+//                    gradient GEMM, which read it back and left 512 slabs to a finish launch
+//   l0_wgrad_finish_kernel  fixed-order sum of the block partials, added into the gradient or
+//                    (registered SGD step, api.h SgdFuse) applied to the master weights
+//   l0_bwd_kernel<1> the dz pass that stores dz for the weight gradient GEMM (ops/layers.py
+//                    L0_WGRAD_FUSE = False; the fused variant's reference), l0_bwd_kernel<0> the
+//                    BN-backward sums through the recomputed z
 // Every pass runs the same conv code on the same inputs, so z is bit-identical to the forward's;
 // the arithmetic of each step is the one of conv_smallk.hip (conv) and bn_act.hip (finalize,
 // apply, first-maximum pool rule).
@@ -28,6 +39,17 @@
 // exchanged with DPP (quad_perm, row_ror:8), no LDS.
 // Measured (profiles/r4k_vgg11_b256_l0v5.md): 12.0 + 19.1 us forward, 15.3 + 17.3 us backward
 // at b256 against ~66 us of conv + BN passes unfused; step 0.835-0.846 vs 0.855 ms same box.
+//
+// Fused weight gradient (l0_bwd_kernel<2>): the conv contracts over (tap, channel) with lane =
+// pixel, the weight gradient contracts over the tile's 16 pixels, so both operands are
+// transposed through a per-wave LDS stage: the bf16 dz tile [16 px][64 ch] is written as the
+// lanes hold it and read back with ds_read_b64_tr_b16 as the A operand (row = channel, k =
+// pixel) of v_mfma_f32_16x16x16_bf16; the tile's 4 x 10 input halo patch (4 of the 8 padded
+// channels) is written from the conv's own fragments and read per lane as the B operand
+// (k = pixel, column = tap * 3 + c: 27 real columns in two 16-column tiles, the five spare
+// columns read the zero pad channel 3). 4 x 2 MFMAs per tile, 32 accumulator registers.
+// Measured (profiles/l0_wgrad_fused.md): 16.5 us + 6.2 us finish at b256 against 18.2 us dz
+// pass + 14.6 us WGRAD GEMM + 5.5 us finish; step 0.7017 vs 0.7389 ms, every trial of the A/B.
 #include "common.h"
 #include "api.h"
 
@@ -63,6 +85,7 @@ struct Args {
                              // the backward sums need nothing else of the window)
   float* dgamma;             // accumulated (arena)
   float* dbeta;
+  float* wg;                 // fused weight gradient: [blocks][64][kWgN] fp32 partials
 };
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
@@ -385,12 +408,49 @@ __global__ __launch_bounds__(256) void l0_sums_kernel(Args a, int windows) {
   }
 }
 
-// BN backward through the recomputed z. APPLY = 0: S1 / S2 sums; 1: dz (+ dgamma / dbeta)
+// ---- weight gradient fused into the dz pass (APPLY = 2)
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+constexpr int kWgN = 28;            // partial's columns: n = tap * 3 + c < 27, + 1 (16-B rows)
+constexpr int kWgSlab = kK * kWgN;  // fp32 per block partial (7 KB)
+// dz tile row: 64 channels + 4 pad = 34 dwords, so the 16 lanes of a ds_write_b64 group (one
+// pixel row each) land on 16 distinct bank pairs
+constexpr int kDzRow = 68;
+struct alignas(16) WgStage {        // per wave
+  unsigned short dz[16][kDzRow];    // this tile's bf16 dz [pixel][channel]
+  unsigned short xp[4 * 10][4];     // its input halo patch [row][column][channels 0..3]
+};
+template <bool ON> struct WgLds { WgStage w[4]; };
+template <> struct WgLds<false> {};
+
+// BN backward through the recomputed z. APPLY = 0: S1 / S2 sums; 1: dz (+ dgamma / dbeta);
+// 2: dz kept on chip and contracted with the input patch into the weight gradient partial
 template <int APPLY>
-__global__ __launch_bounds__(256) void l0_bwd_kernel(Args a) {
+__device__ __forceinline__ void l0_bwd_body(const Args& a) {
+  constexpr bool WG = APPLY == 2;
   __shared__ Smem sm;
-  const int lane = threadIdx.x & 63, g = lane >> 4, rl = lane & 15;
+  __shared__ WgLds<WG> wl;
+  const int lane = threadIdx.x & 63, g = lane >> 4, rl = lane & 15, wib = threadIdx.x >> 6;
   float s1[kNT][4] = {}, s2[kNT][4] = {};
+  // WG: dW[channel jt*16 + 4g + v][column nt*16 + rl] of this wave's tiles
+  f32x4 dwacc[kNT][2];
+  // ... and this lane's B-operand source in the patch: column n = nt*16 + rl = tap * 3 + c at
+  // the tile pixels 4g .. 4g+3 (tile row g >> 1, columns 4 (g & 1) + j; + 4 u16 per pixel);
+  // n >= 27 reads the zero pad channel 3
+  int xoff[2] = {0, 0};
+  if (WG) {
+#pragma unroll
+    for (int jt = 0; jt < kNT; ++jt)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) dwacc[jt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int n = nt * 16 + rl;
+      const int tap = n < 27 ? n / 3 : 0, c = n < 27 ? n - tap * 3 : 3;
+      const int tr = tap / 3, ts = tap - tr * 3;
+      xoff[nt] = (((g >> 1) + tr) * 10 + 4 * (g & 1) + ts) * 4 + c;
+    }
+  }
   tile_loop<true>(
       a, g, rl,
       [&] {
@@ -426,6 +486,19 @@ __global__ __launch_bounds__(256) void l0_bwd_kernel(Args a) {
         }
       },
       [&](const Tile& cur, const Ops& op) {
+        if constexpr (WG) {
+          // the halo patch from the conv's fragments: tap (tr, ts) of pixel (r, c) is patch
+          // position (r + tr, c + ts); positions shared by several lanes get the same value
+          WgStage& st = wl.w[wib];
+#pragma unroll
+          for (int t = 0; t < kNKS; ++t) {
+            const int tap = 4 * t + g;
+            const int tr = tap / 3, ts = tap - tr * 3;
+            if (tap < 9)
+              *reinterpret_cast<uint2*>(st.xp[((rl >> 3) + tr) * 10 + (rl & 7) + ts]) =
+                  make_uint2(op.x[t].x, op.x[t].y);
+          }
+        }
         float z[kNT][4];
         conv_z(sm, op.x, g, rl, z);
         const unsigned cw[kNT] = {op.code.x, op.code.y, op.code.z, op.code.w};
@@ -445,13 +518,133 @@ __global__ __launch_bounds__(256) void l0_bwd_kernel(Args a) {
               s2[j][v] += dyb * (zf * sm.cf[2][c] + sm.cf[3][c]);
             }
           }
-        if (APPLY) {
+        if constexpr (WG) {
+          // dW += dz^T x over the tile's 16 pixels. LDS accesses of one wave complete in
+          // program order, so the wave's own stage needs no barrier, only the compiler's order
+          WgStage& st = wl.w[wib];
+#pragma unroll
+          for (int j = 0; j < kNT; ++j)
+            *reinterpret_cast<u16x4*>(&st.dz[rl][j * 16 + 4 * g]) = o[j];
+          asm volatile("" ::: "memory");
+          const unsigned short* xp = &st.xp[0][0];
+          v4i16 fb[2];
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fb[nt][j] = (short)xp[xoff[nt] + 4 * j];
+          // A operand: lane group g reads pixels 4g .. 4g+3 x channels jt*16 .. +15 transposed
+          // (lane 4q + p supplies row q, columns 4p .. 4p+3; lane i receives column i)
+          const unsigned short* arow = &st.dz[4 * g + (rl >> 2)][4 * (rl & 3)];
+#pragma unroll
+          for (int jt = 0; jt < kNT; ++jt) {
+            const v4i16 fa = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(arow + jt * 16));
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+              dwacc[jt][nt] =
+                  __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(fa, fb[nt], dwacc[jt][nt], 0, 0, 0);
+          }
+        } else if (APPLY) {
           unsigned short* dst = a.dz + (((size_t)cur.n * a.H + cur.h) * a.W + cur.w) * kK + 4 * g;
 #pragma unroll
           for (int j = 0; j < kNT; ++j) *reinterpret_cast<u16x4*>(dst + j * 16) = o[j];
         }
       });
   if (!APPLY) block_sums(s1, s2, a.sums + stat_rep(blockIdx.x) * 2 * kK, rl, g, sm);
+  if constexpr (WG) {
+    // the block's partial: waves summed in the fixed order ((w0 + w1) + w2) + w3 through LDS
+    // (the weight image's space, free after the tile loop), stored by wave 3 as [64][kWgN]
+    float* red = reinterpret_cast<float*>(sm.w);
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (wib == w) {
+#pragma unroll
+        for (int jt = 0; jt < kNT; ++jt)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+              const int e = (jt * 2 + nt) * 4 + v;
+              float t = dwacc[jt][nt][v];
+              if (w > 0) t += red[e * 64 + lane];
+              if (w < 3) {
+                red[e * 64 + lane] = t;
+              } else if (nt * 16 + rl < kWgN) {
+                a.wg[(size_t)blockIdx.x * kWgSlab + (jt * 16 + 4 * g + v) * kWgN + nt * 16 + rl] = t;
+              }
+            }
+      }
+      if (w < 3) __syncthreads();
+    }
+  }
+}
+
+template <int APPLY>
+__global__ __launch_bounds__(256) void l0_bwd_kernel(Args a) {
+  l0_bwd_body<APPLY>(a);
+}
+// the fused variant's 32 accumulators must not cost the pass its 4 waves per SIMD
+template <>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void l0_bwd_kernel<2>(
+    Args a) {
+  l0_bwd_body<2>(a);
+}
+
+// Sum of the fused weight gradient's block partials in fixed order (no atomics: reproducible
+// by construction). A block owns 4 float4 of the [64][kWgN] partial; its 64 slab lanes each
+// sum slabs s, s + 64, ... with kWgBatch loads in flight, then a fixed tree over the lanes.
+// The total is added into the gradient ([K][R][S][3] with wkrsc, else [K][3][R][S])
+// or, with ``sg.p`` (api.h SgdFuse: the layer has no DGRAD, so its weights are read by nothing
+// after this), applied as the optimizer step: master and momentum [K][R][S][3], the bf16
+// operand copy [K][R][S][8] with its pad channels untouched.
+constexpr int kWgBatch = 8;
+__global__ __launch_bounds__(256) void l0_wgrad_finish_kernel(const float* __restrict__ ws,
+                                                              int nslab, float* __restrict__ dw,
+                                                              int wkrsc, SgdFuse sg) {
+  __shared__ float4 red[64][4];
+  const bool opt = sg.p != nullptr;
+  const float lr = opt ? sched_lr_block(sg.sched, sg.lr) : sg.lr;
+  const int e = threadIdx.x & 3, s0 = threadIdx.x >> 2;
+  const int i4 = blockIdx.x * 4 + e;
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int z = s0; z < nslab; z += 64 * kWgBatch) {
+    float4 t[kWgBatch];
+#pragma unroll
+    for (int u = 0; u < kWgBatch; ++u)
+      if (z + 64 * u < nslab)
+        t[u] = reinterpret_cast<const float4*>(ws + (size_t)(z + 64 * u) * kWgSlab)[i4];
+#pragma unroll
+    for (int u = 0; u < kWgBatch; ++u)
+      if (z + 64 * u < nslab) { v.x += t[u].x; v.y += t[u].y; v.z += t[u].z; v.w += t[u].w; }
+  }
+  red[s0][e] = v;
+  for (int h = 32; h >= 1; h >>= 1) {
+    __syncthreads();
+    if (s0 < h) {
+      const float4 o = red[s0 + h][e];
+      v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
+      red[s0][e] = v;
+    }
+  }
+  if (s0 != 0) return;
+  const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int idx = i4 * 4 + t, k = idx / kWgN, n = idx - k * kWgN;
+    if (n >= 27) continue;
+    const int tap = n / 3, c = n - tap * 3;
+    if (opt) {
+      const int mi = k * 27 + n;
+      float b = sg.buf[mi];
+      const float np = sgd_update1(sg.p[mi], vv[t], b, lr, sg.momentum, sg.wd, sg.grad_scale,
+                                   sg.nesterov);
+      sg.p[mi] = np;
+      sg.buf[mi] = b;
+      sg.wc[(k * 9 + tap) * 8 + c] = f2bf(np);
+    } else {
+      dw[wkrsc ? k * 27 + n : (k * 3 + c) * 9 + tap] += vv[t];
+    }
+  }
 }
 
 // one tile per wave where the grid allows, at most 1024 blocks (4 per CU): every block adds one
@@ -512,17 +705,32 @@ extern "C" int ddp_l0_fwd(const ConvGeom* g, const L0Io* io, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// backward: sums pass + dz pass (sums zeroed by the caller; coef = the forward's table)
+// backward: sums pass + dz pass (sums zeroed by the caller; coef = the forward's table). With
+// ``dz`` the dz pass stores dz for the caller's weight gradient GEMM; with ``dw`` and no ``dz``
+// it builds the weight gradient itself (+ the partials' finish, which takes a registered SGD
+// step: the layer has no DGRAD). -2 = the fused form does not serve this call (3 real input
+// channels only; workspace too small): nothing was launched, the caller takes the dz form.
 extern "C" int ddp_l0_bwd(const ConvGeom* g, const L0Io* io, hipStream_t st) {
-  if (!l0_shape_ok(g) || !io->x || !io->wc || !io->coef || !io->dy || !io->sums || !io->dz ||
-      !io->code || !io->zw)
+  const bool fused = !io->dz && io->dw;
+  if (!l0_shape_ok(g) || !io->x || !io->wc || !io->coef || !io->dy || !io->sums ||
+      (!io->dz && !io->dw) || !io->code || !io->zw)
     return -1;
-  const l0::Args a = l0_args(g, io);
+  l0::Args a = l0_args(g, io);
   const unsigned nb = l0::grid_for(a.tiles);
+  if (fused && (g->Creal != 3 || !io->ws || io->ws_elems < (size_t)nb * l0::kWgSlab)) return -2;
   const int windows = g->N * (g->H / 2) * (g->W / 2);
   const unsigned ns = (unsigned)std::max(1, std::min(512, (windows + 127) / 128));
   if (!io->sums_ready)  // (else taken by the next block's dgrad finish, BnBwdFuse::code)
     hipLaunchKernelGGL(l0::l0_sums_kernel, dim3(ns), dim3(256), 0, st, a, windows);
-  hipLaunchKernelGGL(l0::l0_bwd_kernel<1>, dim3(nb), dim3(256), 0, st, a);
+  if (!fused) {
+    hipLaunchKernelGGL(l0::l0_bwd_kernel<1>, dim3(nb), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+  }
+  a.wg = io->ws;
+  hipLaunchKernelGGL(l0::l0_bwd_kernel<2>, dim3(nb), dim3(256), 0, st, a);
+  SgdFuse sg{};
+  if (g->wkrsc) ddp_sgd_fuse_take_final(io->dw, &sg);  // (master and gradient share the layout)
+  hipLaunchKernelGGL(l0::l0_wgrad_finish_kernel, dim3(l0::kWgSlab / 16), dim3(256), 0, st,
+                     (const float*)io->ws, (int)nb, io->dw, g->wkrsc, sg);
   return (int)hipGetLastError();
 }

@@ -388,6 +388,12 @@ L0_FUSE = True
 # separate pass wins (0.5290 vs 0.5333; in-step A/B, every trial: profiles/r6af_ab_constants.jsonl)
 L0_SUMS_IN_FINISH = True
 L0_SUMS_IN_FINISH_MAX_BATCH = 64
+# ... and its weight gradient built inside the dz pass (conv_l0.hip l0_bwd_kernel<2> +
+# l0_wgrad_finish_kernel, which also takes the layer's SGD step): dz, the layer's last
+# full-resolution tensor, is never stored. False: dz stored + the WGRAD GEMM and its finish.
+# b256 0.7017 vs 0.7389 ms, b32 0.3622 vs 0.3672 ms (in-step A/B, faster in every trial:
+# profiles/l0_wgrad_fused_ab.jsonl)
+L0_WGRAD_FUSE = True
 
 
 def l0_serves(spec, x):
@@ -585,15 +591,27 @@ class _ConvBNActFn(torch.autograd.Function):
             gw, gg, gbt = ensure_grad(weight), ensure_grad(gamma), ensure_grad(beta)
             if bias is not None:
                 ensure_grad(bias)  # analytically zero under batch-statistics BN (bn_act.hip)
-            dz = torch.empty(N, H, W, spec.K, dtype=BF16, device=x.device)
             ready, spec.l0_sums_ready = getattr(spec, "l0_sums_ready", False), False
-            native().l0_bwd(spec.geom(N, H, W), ptr(x), ptr(spec.wc), ptr(bias), spec.eps,
-                            int(spec.relu), ptr(spec.coef), ptr(dy), ptr(spec.sums), ptr(dz),
-                            ptr(gg), ptr(gbt), ptr(ctx.l0_code[0]), ptr(ctx.l0_code[1]),
-                            stream_handle(), sums_ready=int(ready))
+            args = (ptr(x), ptr(spec.wc), ptr(bias), spec.eps, int(spec.relu), ptr(spec.coef),
+                    ptr(dy), ptr(spec.sums))
+            tail = (ptr(gg), ptr(gbt), ptr(ctx.l0_code[0]), ptr(ctx.l0_code[1]), stream_handle())
+            fused = L0_WGRAD_FUSE and not ctx.needs_input_grad[0]
+            if fused:
+                # the dz pass builds the weight gradient itself: no dz tensor, no GEMM (1 = this
+                # call is not served, nothing ran: the dz form below)
+                ws = workspace(x.device)
+                fused = not native().l0_bwd(spec.geom(N, H, W, weight_krsc(gw)), *args, 0, *tail,
+                                            sums_ready=int(ready), dw=ptr(gw), ws=ptr(ws),
+                                            ws_elems=ws.numel())
+            if not fused:
+                dz = torch.empty(N, H, W, spec.K, dtype=BF16, device=x.device)
+                native().l0_bwd(spec.geom(N, H, W), *args, ptr(dz), *tail, sums_ready=int(ready))
             ctx.l0_code = None
             spec.l0_code = None
             grad_ready([gamma, beta, bias])
+            if fused:
+                grad_ready([weight])
+                return (None,) * 10
             dx = conv_backward(spec, x, dz, gw, ctx.needs_input_grad[0], ctx.in_link,
                                weight=weight)
             return dx, None, None, None, None, None, None, None, None, None
