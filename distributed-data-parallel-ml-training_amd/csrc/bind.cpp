@@ -549,19 +549,32 @@ PYBIND11_MODULE(_native, m) {
                        uintptr_t buf, float lr, float momentum, float wd, float grad_scale,
                        int nesterov, uintptr_t st, int zero_grad, uintptr_t counter, int delta,
                        uintptr_t skip, uintptr_t shadow, uintptr_t slot, uintptr_t done,
-                       uintptr_t signal, uintptr_t sched, int sched_advance) {
+                       uintptr_t signal, uintptr_t sched, int sched_advance, uintptr_t lars_side,
+                       uintptr_t lars_tensors, uintptr_t lars_partial, uintptr_t lars_trust,
+                       float lars_eta, float lars_eps) {
     check(ddp_sgd_pack(P<void>(items), n_items, P<long long>(descs), P<float>(p), P<float>(g),
                        P<float>(buf), lr, momentum, wd, grad_scale, nesterov, zero_grad,
                        P<int>(counter), delta, P<const unsigned>(skip), P<unsigned short>(shadow),
                        P<float>(slot), P<unsigned>(done), P<unsigned>(signal),
-                       P<ddp_amd::LrSched>(sched), sched_advance, S(st)),
+                       P<ddp_amd::LrSched>(sched), sched_advance, P<void>(lars_side),
+                       P<void>(lars_tensors), P<void>(lars_partial), P<float>(lars_trust),
+                       lars_eta, lars_eps, S(st)),
           "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
      py::arg("nesterov"), py::arg("stream"), py::arg("zero_grad") = 0, py::arg("counter") = 0,
      py::arg("delta") = 0, py::arg("skip") = 0, py::arg("shadow") = 0, py::arg("slot") = 0,
      py::arg("done") = 0, py::arg("signal") = 0, py::arg("sched") = 0,
-     py::arg("sched_advance") = 0);
+     py::arg("sched_advance") = 0, py::arg("lars_side") = 0, py::arg("lars_tensors") = 0,
+     py::arg("lars_partial") = 0, py::arg("lars_trust") = 0, py::arg("lars_eta") = 0.f,
+     py::arg("lars_eps") = 0.f);
+  // LARS norms launch (optim.hip lars_norms_kernel): per-chunk {sum p^2, sum (g * grad_scale)^2}
+  m.def("lars_norms", [](uintptr_t items, int n_items, uintptr_t p, uintptr_t g, float grad_scale,
+                         uintptr_t partial, uintptr_t st) {
+    check(ddp_lars_norms(P<void>(items), n_items, P<float>(p), P<float>(g), grad_scale,
+                         P<void>(partial), S(st)), "lars_norms");
+  }, py::arg("items"), py::arg("n_items"), py::arg("p"), py::arg("g"), py::arg("grad_scale"),
+     py::arg("partial"), py::arg("stream"));
   // descs: list of (p, wc, wt, K, Cr, C, R, S, krsc) as in pack_conv_weights
   m.def("shard_tail", [](uintptr_t segs, int n_segs, uintptr_t src, uintptr_t dst,
                          std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int, int,

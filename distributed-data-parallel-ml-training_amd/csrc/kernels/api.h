@@ -358,7 +358,16 @@ int ddp_sgd_pack(const void* items, int n_items, const long long* descs, float* 
                  float* buf, float lr, float momentum, float wd, float grad_scale, int nesterov,
                  int zero_grad, int* counter, int delta, const unsigned* skip,
                  unsigned short* shadow, float* slot, unsigned* done, unsigned* signal,
-                 ddp_amd::LrSched* sched, int sched_advance, hipStream_t st);
+                 ddp_amd::LrSched* sched, int sched_advance, const void* lars_side,
+                 const void* lars_tensors, const void* lars_partial, float* lars_trust,
+                 float lars_eta, float lars_eps, hipStream_t st);
+// LARS (optim.hip LarsArgs, optim/lars.py): ``lars_side`` non-null selects the LARS instantiation
+// of ddp_sgd_pack — int2 per work item {parameter | -1, first item of its tensor}, ``lars_tensors``
+// int4 per parameter {first global chunk, chunks, adapted, -}, ``lars_partial`` float2 per global
+// chunk as written by ddp_lars_norms, launched before it on the same stream: int4 items
+// {arena offset, count <= 8192, global chunk, -}, one block each
+int ddp_lars_norms(const void* items, int n_items, const float* p, const float* g,
+                   float grad_scale, void* partial, hipStream_t st);
 // tail of a pipelined step with sharded buckets: gathered small-tensor slots -> fp32 arena,
 // re-pack of channel-padded conv operands, then release-increment ``signal`` (optim.hip)
 int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,

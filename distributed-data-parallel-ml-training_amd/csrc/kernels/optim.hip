@@ -168,13 +168,29 @@ __device__ __forceinline__ void sched_stage(LrSched* s) {
   __hip_atomic_store(&s->next, k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper& h) {
-  return sgd_update1(p, g, b, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+// One element update of the fused launch. LARS = false: sgd_update1, ``trust`` unused (the
+// plain instantiation compiles to what it was before LARS existed). LARS = true: the same fma
+// chain with the weight-decayed gradient multiplied by the tensor's trust ratio first (a ratio
+// of exactly 1.0 reproduces the plain update bit for bit).
+template <bool LARS>
+__device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper& h, float trust) {
+  if constexpr (!LARS) {
+    return sgd_update1(p, g, b, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+  } else {
+    float d = trust * __builtin_fmaf(h.wd, p, g * h.grad_scale);
+    if (h.momentum != 0.f) {
+      b = __builtin_fmaf(h.momentum, b, d);
+      d = h.nesterov ? __builtin_fmaf(h.momentum, b, d) : b;
+    }
+    return __builtin_fmaf(-h.lr, d, p);
+  }
 }
 
+template <bool LARS>
 __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* __restrict__ descs,
                               float* __restrict__ p, float* __restrict__ g,
-                              float* __restrict__ buf, const SgdHyper& h, float* tile);
+                              float* __restrict__ buf, const SgdHyper& h, float* tile,
+                              float trust);
 
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
                                                        const long long* __restrict__ descs,
@@ -184,13 +200,128 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
   __shared__ float tile[kTileElems];
   h.lr = sched_lr_block(h.sched, h.lr);
   if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
-  sgd_pack_body(items, descs, p, g, buf, h, tile);
+  sgd_pack_body<false>(items, descs, p, g, buf, h, tile, 1.f);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
+// ---------------------------------------------------------------------------------------------
+// LARS (You et al. 2017; optim/lars.py): every adapted tensor's update is multiplied by its
+// trust ratio eta * |w| / (|g * grad_scale| + wd * |w| + eps), both norms over the tensor's own
+// elements. Two launches, no float atomics, so the result does not depend on block scheduling:
+//   1) lars_norms_kernel: one block per 8192-element chunk (the chunking of the SGD items) stores
+//      {sum p^2, sum (g * grad_scale)^2} of its chunk into the slot of the chunk's GLOBAL number
+//      (numbered over the whole arena: per-bucket launches on different streams never share one);
+//   2) lars_pack_kernel, the LARS instantiation of the fused SGD + re-pack body: wave 0 of every
+//      block sums its tensor's partials in one fixed order (lane l adds chunks l, l + 64, ...
+//      serially, then wave_sum), computes the ratio and broadcasts it through LDS; the block
+//      that owns the tensor's first work item also stores it for the host (LARS.trust_ratios).
+// The norms are read from memory the first launch wrote, so a zero_grad in the second one is safe.
+struct LarsArgs {
+  const int2* side;       // per work item: {parameter index | -1 (no ratio: item 5), first item}
+  const int4* tensors;    // per parameter: {first global chunk, chunks, adapted, -}
+  const float2* partial;  // per global chunk: {sum p^2, sum (g * grad_scale)^2}
+  float* trust;           // per parameter (written)
+  float eta, eps;
+};
+
+constexpr int kNormChunk = 8192;  // elements per norm block (optim/lars.py LARS.CHUNK)
+
+__global__ __launch_bounds__(256) void lars_norms_kernel(const int4* __restrict__ items,
+                                                         const float* __restrict__ p,
+                                                         const float* __restrict__ g,
+                                                         float grad_scale,
+                                                         float2* __restrict__ partial) {
+  // {arena offset (multiple of 4), count <= kNormChunk, global chunk number, -}
+  const int4 it = items[blockIdx.x];
+  const size_t off = (size_t)(unsigned)it.x;
+  const int cnt = it.y, n4 = cnt >> 2;
+  const int tid = threadIdx.x;
+  const float4* p4 = reinterpret_cast<const float4*>(p + off);
+  const float4* g4 = reinterpret_cast<const float4*>(g + off);
+  constexpr int kIter = kNormChunk / (256 * 4);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 pv[kIter], gv[kIter];
+#pragma unroll
+  for (int j = 0; j < kIter; ++j) {  // every 16-byte load of the chunk in flight at once
+    const int i = tid + 256 * j;
+    pv[j] = i < n4 ? p4[i] : z;
+    gv[j] = i < n4 ? g4[i] : z;
+  }
+  float sp = 0.f, sg = 0.f;  // one serial fma chain per thread: 4 * kIter (+ 1 tail) terms
+#pragma unroll
+  for (int j = 0; j < kIter; ++j) {
+    const float* pp = &pv[j].x;
+    const float* gg = &gv[j].x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gs = gg[e] * grad_scale;
+      sp = __builtin_fmaf(pp[e], pp[e], sp);
+      sg = __builtin_fmaf(gs, gs, sg);
+    }
+  }
+  const int t = (n4 << 2) + tid;  // scalar tail: numel not a multiple of 4
+  if (t < cnt) {
+    const float pt = p[off + t], gs = g[off + t] * grad_scale;
+    sp = __builtin_fmaf(pt, pt, sp);
+    sg = __builtin_fmaf(gs, gs, sg);
+  }
+  sp = wave_sum(sp);
+  sg = wave_sum(sg);
+  __shared__ float2 s_w[4];
+  if ((tid & 63) == 0) s_w[tid >> 6] = make_float2(sp, sg);
+  __syncthreads();
+  if (tid == 0) {
+    partial[it.z] = make_float2(((s_w[0].x + s_w[1].x) + s_w[2].x) + s_w[3].x,
+                                ((s_w[0].y + s_w[1].y) + s_w[2].y) + s_w[3].y);
+  }
+}
+
+// This block's trust ratio (1.0: excluded tensor, zero norm, item without an update). Every
+// condition but the partial loop's trip count is uniform over the block.
+__device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd) {
+  __shared__ float s_trust;
+  if (threadIdx.x < 64) {
+    const int2 sd = a.side[blockIdx.x];
+    float t = 1.f;
+    if (sd.x >= 0) {
+      const int4 tn = a.tensors[sd.x];
+      if (tn.z) {
+        float sp = 0.f, sg = 0.f;
+        for (int c = threadIdx.x; c < tn.y; c += 64) {
+          const float2 v = a.partial[tn.x + c];
+          sp += v.x;
+          sg += v.y;
+        }
+        const float wn = sqrtf(wave_sum(sp)), gn = sqrtf(wave_sum(sg));
+        if (wn > 0.f && gn > 0.f) t = a.eta * wn / (gn + wd * wn + a.eps);
+      }
+      if (sd.y && threadIdx.x == 0) a.trust[sd.x] = t;
+    }
+    if (threadIdx.x == 0) s_trust = t;
+  }
+  __syncthreads();
+  return s_trust;
+}
+
+__global__ __launch_bounds__(256) void lars_pack_kernel(const int4* __restrict__ items,
+                                                        const long long* __restrict__ descs,
+                                                        float* __restrict__ p,
+                                                        float* __restrict__ g,
+                                                        float* __restrict__ buf, SgdHyper h,
+                                                        LarsArgs la) {
+  __shared__ float tile[kTileElems];
+  h.lr = sched_lr_block(h.sched, h.lr);
+  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
+  const float trust = lars_trust_block(la, h.wd);
+  sgd_pack_body<true>(items, descs, p, g, buf, h, tile, trust);
+  if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
+}
+
+template <bool LARS>
 __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* __restrict__ descs,
                               float* __restrict__ p, float* __restrict__ g,
-                              float* __restrict__ buf, const SgdHyper& h, float* tile) {
+                              float* __restrict__ buf, const SgdHyper& h, float* tile,
+                              float trust) {
   const int4 it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
@@ -203,17 +334,17 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
         float4 pv = *reinterpret_cast<float4*>(p + off + i);
         const float4 gv = *reinterpret_cast<const float4*>(g + off + i);
         float4 bv = *reinterpret_cast<float4*>(buf + off + i);
-        pv.x = sgd1(pv.x, gv.x, bv.x, h);
-        pv.y = sgd1(pv.y, gv.y, bv.y, h);
-        pv.z = sgd1(pv.z, gv.z, bv.z, h);
-        pv.w = sgd1(pv.w, gv.w, bv.w, h);
+        pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
+        pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
+        pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
+        pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
         *reinterpret_cast<float4*>(p + off + i) = pv;
         *reinterpret_cast<float4*>(buf + off + i) = bv;
         if (h.zero_grad) *reinterpret_cast<float4*>(g + off + i) = make_float4(0.f, 0.f, 0.f, 0.f);
       } else {
         for (int e = i; e < min(cnt, i + 4); ++e) {
           float b = buf[off + e];
-          p[off + e] = sgd1(p[off + e], g[off + e], b, h);
+          p[off + e] = sgd1<LARS>(p[off + e], g[off + e], b, h, trust);
           buf[off + e] = b;
           if (h.zero_grad) g[off + e] = 0.f;
         }
@@ -233,10 +364,10 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
       float4 pv = *reinterpret_cast<float4*>(p + off + i);
       const float4 gv = *reinterpret_cast<const float4*>(g + off + i);
       float4 bv = *reinterpret_cast<float4*>(buf + off + i);
-      pv.x = sgd1(pv.x, gv.x, bv.x, h);
-      pv.y = sgd1(pv.y, gv.y, bv.y, h);
-      pv.z = sgd1(pv.z, gv.z, bv.z, h);
-      pv.w = sgd1(pv.w, gv.w, bv.w, h);
+      pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
+      pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
+      pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
+      pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
       *reinterpret_cast<float4*>(p + off + i) = pv;
       *reinterpret_cast<float4*>(buf + off + i) = bv;
       if (h.zero_grad) *reinterpret_cast<float4*>(g + off + i) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -284,10 +415,10 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
       float4 pv = *reinterpret_cast<float4*>(p + base + i);
       const float4 gv = *reinterpret_cast<const float4*>(g + base + i);
       float4 bv = *reinterpret_cast<float4*>(buf + base + i);
-      pv.x = sgd1(pv.x, gv.x, bv.x, h);
-      pv.y = sgd1(pv.y, gv.y, bv.y, h);
-      pv.z = sgd1(pv.z, gv.z, bv.z, h);
-      pv.w = sgd1(pv.w, gv.w, bv.w, h);
+      pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
+      pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
+      pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
+      pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
       *reinterpret_cast<float4*>(p + base + i) = pv;
       *reinterpret_cast<float4*>(buf + base + i) = bv;
       if (h.zero_grad) *reinterpret_cast<float4*>(g + base + i) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -318,7 +449,7 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
       const int kl = idx / run, e = idx - kl * run;
       const size_t gi = poff + (size_t)(k0 + kl) * Cr * RS + (size_t)c0 * RS + e;
       float b = buf[gi];
-      const float np = sgd1(p[gi], g[gi], b, h);
+      const float np = sgd1<LARS>(p[gi], g[gi], b, h, trust);
       p[gi] = np;
       buf[gi] = b;
       if (h.zero_grad) g[gi] = 0.f;
@@ -331,7 +462,7 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
       const int rs = t % RS, kl = t / RS;
       const size_t gi = poff + ((size_t)(k0 + kl) * RS + rs) * Cr + c0 + cl;
       float b = buf[gi];
-      const float np = sgd1(p[gi], g[gi], b, h);
+      const float np = sgd1<LARS>(p[gi], g[gi], b, h, trust);
       p[gi] = np;
       buf[gi] = b;
       if (h.zero_grad) g[gi] = 0.f;
@@ -452,12 +583,30 @@ extern "C" int ddp_sgd_pack(const void* items, int n_items, const long long* des
                             float grad_scale, int nesterov, int zero_grad, int* counter,
                             int delta, const unsigned* skip, unsigned short* shadow, float* slot,
                             unsigned* done, unsigned* signal, LrSched* sched, int sched_advance,
-                            hipStream_t st) {
+                            const void* lars_side, const void* lars_tensors,
+                            const void* lars_partial, float* lars_trust, float lars_eta,
+                            float lars_eps, hipStream_t st) {
   SgdHyper h{lr, momentum, wd, grad_scale, nesterov, zero_grad, counter, delta, skip, shadow, slot,
              done, signal, sched, sched && sched_advance ? 1 : 0};
   if (n_items <= 0) return 0;
+  if (lars_side) {
+    if (!lars_tensors || !lars_partial || !lars_trust) return -1;
+    LarsArgs la{(const int2*)lars_side, (const int4*)lars_tensors, (const float2*)lars_partial,
+                lars_trust, lars_eta, lars_eps};
+    hipLaunchKernelGGL(lars_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items,
+                       descs, p, g, buf, h, la);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(sgd_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, descs,
                      p, g, buf, h);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ddp_lars_norms(const void* items, int n_items, const float* p, const float* g,
+                              float grad_scale, void* partial, hipStream_t st) {
+  if (n_items <= 0) return 0;
+  hipLaunchKernelGGL(lars_norms_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, p, g,
+                     grad_scale, (float2*)partial);
   return (int)hipGetLastError();
 }
 

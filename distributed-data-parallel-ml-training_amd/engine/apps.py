@@ -17,10 +17,9 @@ import torch
 from .. import SEED
 from ..data import SyntheticCIFAR10, make_loader
 from ..models import build
-from ..optim import FusedSGD
 from ..parallel import (DistributedDataParallel, STRATEGIES, destroy, init_distributed_setup,
                         make_communicator, test_distributed_setup)
-from ..utils.cli import lr_schedule_from_args
+from ..utils.cli import lr_schedule_from_args, optimizer_from_args
 from ..utils import MetricsSink, Watchdog, load_checkpoint, local_rank_of, parse_all, pick_device, \
     save_checkpoint, seed_everything
 from .trainer import CrossEntropyLoss, test_model, train_model, train_model_graph
@@ -63,7 +62,7 @@ def main(part, argv=None):
                                         captured=captured)
     # --lr / --lr-schedule ... (opt-in; default: the reference's constant 0.1, nothing attached)
     lr, schedule = lr_schedule_from_args(args, len(train_loader))
-    optimizer = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=0.0001)
+    optimizer = optimizer_from_args(args, model.parameters(), lr)  # --optimizer sgd | lars
     if schedule is not None:
         optimizer.set_schedule(schedule)
     if args.resume:

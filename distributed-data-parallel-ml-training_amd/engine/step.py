@@ -74,8 +74,10 @@ class TrainStep:
         # its WGRAD finish and the update) -> each conv weight's update runs in the split-K
         # finish that completes its gradient; the step's SGD launch covers only the rest
         # (optim/sgd.py register_in_backward). DDP_AMD_SGD_IN_BWD=0 keeps the separate pass.
+        # LARS needs the norm of the whole gradient before any element moves: never in the backward.
         self.opt_in_bwd = (self.fold_opt and sync is None and sgd_in_backward_ok(model)
-                           and hasattr(optimizer, "register_in_backward"))
+                           and hasattr(optimizer, "register_in_backward")
+                           and not getattr(optimizer, "needs_whole_tensors", False))
 
     def _fused_loss(self):
         """Use the model's fused classifier+loss when the criterion is the plain mean CE."""
@@ -339,6 +341,11 @@ class SegmentedDDPStep(TrainStep):
             raise ValueError(f"per-bucket update plan {update} does not match "
                              f"{len(self.buckets)} buckets")
         self.update = update
+        if getattr(optimizer, "needs_whole_tensors", False) and (zero or "s16" in update):
+            # the sharded updates hand each rank a slice of a tensor: no per-tensor norm (LARS)
+            raise ValueError(f"{type(optimizer).__name__} needs whole tensors: the sharded "
+                             "updates (zero=True, \"s16\" buckets) split them across ranks; "
+                             "use update=\"allreduce\"")
         self.zero = None
         self.shard16 = None
         if zero:

@@ -1,0 +1,222 @@
+"""LARS: layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017) on top of the fused SGD.
+
+Large-batch training multiplies the learning rate by the batch ratio (utils/cli.py
+``--lr-ref-batch``); a conv net with BatchNorm tolerates that rate only when each tensor's update
+is scaled to the size of the tensor itself. All arithmetic is fp32; ``gs`` = ``grad_scale``:
+
+    adapted_i = p_i.dim() > 1 or not exclude_1d
+    wn = sqrt(sum(p_i^2));  gn = sqrt(sum((g_i * gs)^2))          (the tensor's own elements)
+    trust_i = eta * wn / (gn + wd * wn + eps)   if adapted_i and wn > 0 and gn > 0   else 1.0
+    d   = trust_i * fma(wd, p, g * gs)
+    buf = fma(momentum, buf, d);  d = nesterov ? fma(momentum, buf, d) : buf
+    p   = fma(-lr, d, p)
+
+A tensor whose ratio is 1.0 takes the plain SGD update bit for bit; weight decay stays on for
+every tensor. Conv masters are stored [K][R][S][C] on the GPU: a norm does not depend on the
+element order.
+
+GPU: two launches per update launch of FusedSGD, both captured with the step
+(csrc/kernels/optim.hip): ``lars_norms_kernel`` writes one {sum p^2, sum (g gs)^2} partial per
+8192-element chunk of every adapted tensor in the range, into the slot of the chunk's number in
+the WHOLE arena (per-bucket launches on the comm stream never share a slot), and the LARS
+instantiation of the fused SGD + re-pack kernel sums its tensor's partials in a fixed order in
+every block's prologue. No float atomics, no host sync: the result is reproducible and does not
+depend on the launch's parameter range. The partial and ratio buffers are allocated once, so
+their addresses survive re-captures.
+
+What LARS cannot do: an update that runs before the whole gradient exists (SGD in the backward)
+or that sees only a shard of a tensor (ZeRO-1, the bf16-gather sharded update) has no norm to
+use. Those paths refuse this optimizer; the all-reduce update (``update="allreduce"``) is the
+one to use.
+"""
+import torch
+
+from .sgd import FusedSGD
+
+_SHARDED = ("LARS needs every tensor's whole gradient for its norm: the sharded updates split "
+            "tensors across ranks; use the replicated update, update=\"allreduce\"")
+
+
+class LARS(FusedSGD):
+    needs_whole_tensors = True
+    CHUNK = 8192  # elements per norm block (optim.hip kNormChunk; the SGD items' chunking)
+
+    def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                 nesterov=False, grad_scale=1.0, trust_coefficient=0.001, eps=1e-8,
+                 exclude_1d=True):
+        if dampening != 0.0:
+            raise ValueError("LARS supports dampening=0 only")
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening,
+                         weight_decay=weight_decay, nesterov=nesterov, grad_scale=grad_scale)
+        if len(self.param_groups) != 1:
+            raise ValueError("LARS supports a single param group")
+        hyper = {"trust_coefficient": float(trust_coefficient), "eps": float(eps),
+                 "exclude_1d": bool(exclude_1d)}
+        self.defaults.update(hyper)
+        self.param_groups[0].update(hyper)
+        self._trust_cpu = None
+        if self._fused:
+            a, dev = self.arena, self.arena.data.device
+            self._chunk0, c = [], 0
+            for n in a.numels:
+                self._chunk0.append(c)
+                c += -(-n // self.CHUNK)
+            # allocated once: captured launches keep these addresses
+            self._lars_partial = torch.zeros(max(c, 1), 2, dtype=torch.float32, device=dev)
+            self._lars_trust = torch.ones(len(a.params), dtype=torch.float32, device=dev)
+            self._lars_tensors = torch.zeros(len(a.params), 4, dtype=torch.int32, device=dev)
+            self._adapted_for = None
+            self._norm_tables = {}
+            self._side_tables, self._side_for = {}, None
+
+    # ------------------------------------------------------------------------------- tables
+    def _adapted(self):
+        ex = bool(self.param_groups[0]["exclude_1d"])
+        return [p.dim() > 1 or not ex for p in self.param_groups[0]["params"]]
+
+    def _tensor_table(self):
+        """Per parameter {first global chunk, chunks, adapted, -}: written in place when
+        ``exclude_1d`` changes (not inside a capture: change it before capturing)."""
+        ex = bool(self.param_groups[0]["exclude_1d"])
+        if self._adapted_for != ex:
+            ad, a = self._adapted(), self.arena
+            rows = [[self._chunk0[i], -(-a.numels[i] // self.CHUNK), int(ad[i]), 0]
+                    for i in range(len(a.params))]
+            self._lars_tensors.copy_(torch.tensor(rows, dtype=torch.int32))
+            self._adapted_for = ex
+            self._norm_tables = {}
+        return self._lars_tensors
+
+    def _norm_table(self, rng):
+        """Work items of the norms launch over parameters [i0, i1): one per chunk of every
+        adapted tensor, {arena offset, count, global chunk number, -}."""
+        t = self._norm_tables.get(rng)
+        if t is None:
+            a, ad = self.arena, self._adapted()
+            rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c, 0]
+                    for i in range(*rng) if ad[i]
+                    for c, s0 in enumerate(range(0, a.numels[i], self.CHUNK))]
+            t = (torch.tensor(rows, dtype=torch.int32, device=a.data.device) if rows else None,
+                 len(rows))
+            self._norm_tables[rng] = t
+        return t
+
+    def _side_table(self, key):
+        """Side table parallel to the work-item table ``key`` of FusedSGD._work_table: per item
+        {parameter index | -1, 1 on the tensor's first item (that block stores the ratio)}."""
+        if self._side_for is not self._tables:  # the work tables were rebuilt
+            self._side_tables, self._side_for = {}, self._tables
+        t = self._side_tables.get(key)
+        if t is None:
+            seen, rows = set(), []
+            for i in self._tables[key][2]:
+                rows.append([i, int(i >= 0 and i not in seen)])
+                seen.add(i)
+            t = torch.tensor(rows, dtype=torch.int32, device=self.arena.data.device)
+            self._side_tables[key] = t
+        return t
+
+    def trust_ratios(self):
+        """Per-parameter trust ratios of the last update of each tensor (1.0: not adapted, or a
+        zero norm). GPU: the device array the update kernel writes, as is (no sync)."""
+        if self._fused:
+            return self._lars_trust
+        if self._trust_cpu is None:
+            self._trust_cpu = torch.ones(len(self.param_groups[0]["params"]))
+        return self._trust_cpu
+
+    # ------------------------------------------------------------------------------ refusals
+    def register_in_backward(self):
+        raise RuntimeError("LARS cannot run in the backward: a tensor's gradient norm exists "
+                           "only once its whole gradient does (TrainStep keeps opt_in_bwd False)")
+
+    def step_elements(self, lo, hi, **kw):
+        raise ValueError(_SHARDED)
+
+    # ---------------------------------------------------------------------------------- step
+    @torch.no_grad()
+    def _cpu_step(self, params):
+        g = self.param_groups[0]
+        lr = self._cpu_lr()
+        m, wd, nesterov = float(g["momentum"]), float(g["weight_decay"]), bool(g["nesterov"])
+        eta, eps = float(g["trust_coefficient"]), float(g["eps"])
+        gs = float(self._grad_scale_factor)
+        plist, adapted, trust = g["params"], self._adapted(), self.trust_ratios()
+        for i in range(*(params if params is not None else (0, len(plist)))):
+            p = plist[i]
+            if p.grad is None:
+                continue
+            gr = p.grad * gs
+            d = gr.add(p, alpha=wd)
+            t = torch.ones((), dtype=torch.float32)
+            if adapted[i]:
+                wn, gn = p.pow(2).sum().sqrt(), gr.pow(2).sum().sqrt()
+                if wn > 0 and gn > 0:
+                    t = eta * wn / (gn + wd * wn + eps)
+            trust[i] = t
+            d = d * t
+            if m != 0:
+                st = self.state[p]
+                if "momentum_buffer" not in st:  # zero start == torch's first-step clone
+                    st["momentum_buffer"] = torch.zeros_like(p)
+                buf = st["momentum_buffer"]
+                buf.mul_(m).add_(d)
+                d = d.add(buf, alpha=m) if nesterov else buf
+            p.add_(d, alpha=-lr)
+
+    @torch.no_grad()
+    def step(self, closure=None, zero_grad=False, counter=None, skip=None, params=None,
+             stream=None, fused_taken=False, signal=None, lr_advance=None):
+        """FusedSGD.step with the trust ratios: one norms launch over the adapted tensors of
+        the range, then the update launch (same arguments, same captured behaviour)."""
+        if fused_taken:
+            raise RuntimeError("LARS: no update is taken in the backward (fused_taken)")
+        if lr_advance is None:
+            lr_advance = params is None
+        if not self._fused:
+            out = closure() if closure is not None else None
+            self._cpu_step(params)
+            if lr_advance:
+                self.count_step()
+            if zero_grad:
+                self.zero_grad()
+            return out
+        from ..ops.common import native, stream_handle
+        g = self.param_groups[0]
+        s = stream.cuda_stream if stream is not None else stream_handle()
+        a = self.arena
+        rng = tuple(params) if params is not None else (0, len(a.params))
+        items, n_items, descs = self._work_table(params)
+        side = self._side_table((rng, frozenset(), frozenset()))
+        tensors = self._tensor_table()
+        nitems, n_norm = self._norm_table(rng)
+        gs = float(self._grad_scale_factor)
+        if n_norm:
+            native().lars_norms(nitems.data_ptr(), n_norm, a.data.data_ptr(), a.grad.data_ptr(),
+                                gs, self._lars_partial.data_ptr(), s)
+        native().sgd_pack(items.data_ptr(), n_items, descs.data_ptr(), a.data.data_ptr(),
+                          a.grad.data_ptr(), self.momentum_buffer.data_ptr(), float(g["lr"]),
+                          float(g["momentum"]), float(g["weight_decay"]), gs,
+                          int(bool(g["nesterov"])), s,
+                          zero_grad=int(bool(zero_grad)),
+                          counter=int(counter[0]) if counter else 0,
+                          delta=int(counter[1]) if counter else 0,
+                          skip=int(skip) if skip else 0,
+                          done=int(signal[0]) if signal else 0,
+                          signal=int(signal[1]) if signal else 0,
+                          lars_side=side.data_ptr(), lars_tensors=tensors.data_ptr(),
+                          lars_partial=self._lars_partial.data_ptr(),
+                          lars_trust=self._lars_trust.data_ptr(),
+                          lars_eta=float(g["trust_coefficient"]), lars_eps=float(g["eps"]),
+                          **self._sched_kw(lr_advance))
+        self._sched_commit(lr_advance, s)
+        return None
+
+    def load_state_dict(self, sd):
+        out = super().load_state_dict(sd)
+        if sd.get("param_groups"):
+            g, saved = self.param_groups[0], sd["param_groups"][0]
+            g["trust_coefficient"] = float(saved.get("trust_coefficient", g["trust_coefficient"]))
+            g["eps"] = float(saved.get("eps", g["eps"]))
+            g["exclude_1d"] = bool(saved.get("exclude_1d", g["exclude_1d"]))
+        return out

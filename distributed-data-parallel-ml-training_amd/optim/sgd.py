@@ -22,6 +22,10 @@ from .schedule import LRSchedule
 
 
 class FusedSGD(torch.optim.SGD):
+    # True for an optimizer whose update of one element needs the whole tensor (optim/lars.py):
+    # the updates that split tensors across ranks or run before a gradient is complete refuse it
+    needs_whole_tensors = False
+
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, grad_scale=1.0):
         params = list(params)
@@ -241,14 +245,16 @@ class FusedSGD(torch.optim.SGD):
                 if not self._per_param[i] or any(it[0] != 2 for it in self._per_param[i]):
                     raise RuntimeError(f"parameter {i}: no elementwise re-pack layout")
             # conv re-pack items first (the heavier tiles start early), then elementwise items
-            sel = [it for i in keep for it in self._per_param[i] if it[0] != 0] + \
-                  [[5] + it[1:] for i in packs for it in self._per_param[i]] + \
-                  [it for i in keep for it in self._per_param[i] if it[0] == 0]
+            # (owner parameter, item) pairs; a re-pack-only item updates nothing: owner -1
+            own = [(i, it) for i in keep for it in self._per_param[i] if it[0] != 0] + \
+                  [(-1, [5] + it[1:]) for i in packs for it in self._per_param[i]] + \
+                  [(i, it) for i in keep for it in self._per_param[i] if it[0] == 0]
+            sel = [it for _, it in own]
             if not sel and not exclude:
                 raise ValueError(f"no parameters in range {rng}")
             items = (torch.tensor(sel, dtype=torch.int32, device=a.data.device) if sel
                      else None)
-            t = (items, len(sel))
+            t = (items, len(sel), [i for i, _ in own])
             self._tables[(rng, exclude, pack_only)] = t
         return t[0], t[1], self._descs
 

@@ -31,6 +31,9 @@ class ShardedUpdate:
         ceil(n/w) elements, the rest floor(n/w) — and its collectives run on a [w, ceil(n/w)]
         zero-padded staging image (two strided copies in, two out) so every rank's
         reduce-scatter / all-gather chunk has the same size."""
+        if getattr(optimizer, "needs_whole_tensors", False):
+            raise ValueError(f"{type(optimizer).__name__} needs whole tensors: a sharded update "
+                             "splits them across ranks; use update=\"allreduce\"")
         self.arena, self.opt, self.comm = arena, optimizer, comm
         self.world, self.rank = comm.world, comm.rank
         self.buckets = [tuple(map(tuple, b)) for b in buckets]
@@ -200,6 +203,9 @@ class ShardedBf16Update:
     ``self.master`` (tests/test_zero_cpu.py compares it with a replicated twin)."""
 
     def __init__(self, arena, optimizer, comm, buckets, which=None, emulate_world=None):
+        if getattr(optimizer, "needs_whole_tensors", False):
+            raise ValueError(f"{type(optimizer).__name__} needs whole tensors: a sharded update "
+                             "splits them across ranks; use update=\"allreduce\"")
         self.arena, self.opt, self.comm = arena, optimizer, comm
         self.cuda = arena.data.is_cuda
         self.rank = comm.rank

@@ -72,7 +72,23 @@ def build_parser(description=None, distributed=True):
     g.add_argument('--min-lr', type=float, default=0.0, help='end value of cosine / linear')
     g.add_argument('--lr-ref-batch', type=int, default=None,
                    help='linear scaling rule: lr *= global batch / this batch')
+    g.add_argument('--optimizer', default='sgd', choices=['sgd', 'lars'],
+                   help='sgd (reference) | lars: every weight tensor\'s update scaled by its trust '
+                        'ratio eta |w| / (|g| + wd |w| + eps), for the learning rates that the '
+                        'linear scaling rule gives a large global batch (works inside --graph)')
+    g.add_argument('--lars-eta', type=float, default=0.001, help='LARS trust coefficient')
+    g.add_argument('--lars-eps', type=float, default=1e-8)
     return p
+
+
+def optimizer_from_args(args, params, lr):
+    """The run's optimizer: the reference's SGD(lr, 0.9, 1e-4), or LARS over the same
+    hyper-parameters with --optimizer lars (biases and BatchNorm vectors are not adapted)."""
+    from ..optim import FusedSGD, LARS
+    if getattr(args, "optimizer", "sgd") == "lars":
+        return LARS(params, lr=lr, momentum=0.9, weight_decay=0.0001,
+                    trust_coefficient=args.lars_eta, eps=args.lars_eps)
+    return FusedSGD(params, lr=lr, momentum=0.9, weight_decay=0.0001)
 
 
 def lr_schedule_from_args(args, steps_per_epoch):
