@@ -41,9 +41,12 @@ def _includes():
 
 # build variants: name -> (module file stem, object dir, extra defines). "det" is the
 # deterministic-statistics test build (csrc/kernels/api.h kStatRep; loaded by _ext.load() when
-# DDP_AMD_DETERMINISTIC=1).
+# DDP_AMD_DETERMINISTIC=1). "stamps" is a diagnostic build that build() does not make by default:
+# the conv GEMM kernels record per-item cycle stamps (csrc/kernels/common.h ConvStampBuf); it is
+# built and loaded by tools/probes/conv_item_stamps.py only.
 VARIANTS = {"release": ("_native", "native", []),
-            "det": ("_native_det", "native_det", ["-DDDP_AMD_DETERMINISTIC"])}
+            "det": ("_native_det", "native_det", ["-DDDP_AMD_DETERMINISTIC"]),
+            "stamps": ("_native_stamps", "native_stamps", ["-DDDP_CONV_STAMPS"])}
 
 
 def ext_path(variant="release"):
@@ -160,5 +163,6 @@ def _build_variant(variant, verbose=True, jobs=None):
 
 
 if __name__ == "__main__":
-    build(verbose=True)
+    # python -m ddp_amd._build [variant ...]   (default: the two shipped builds)
+    build(verbose=True, variants=tuple(sys.argv[1:]) or ("release", "det"))
     sys.exit(0)

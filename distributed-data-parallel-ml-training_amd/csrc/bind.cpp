@@ -529,6 +529,9 @@ PYBIND11_MODULE(_native, m) {
   });
   m.def("conv_force_tile", [](int t, int stages) { ddp_conv_force_tile(t, stages); },
         py::arg("tile_plus_one"), py::arg("stages") = 0);
+#ifdef DDP_CONV_STAMPS
+  m.def("conv_stamps_set", [](uintptr_t buf, int cap) { ddp_conv_stamps_set(P<void>(buf), cap); });
+#endif
   // descs: list of (p, wc, wt, K, Cr, C, R, S, krsc)
   m.def("pack_conv_weights", [](std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int,
                                                        int, int, int, int>> descs, uintptr_t st) {

@@ -351,6 +351,11 @@ int ddp_conv_dense2x2_ok(const ddp_amd::ConvGeom* g);
 void ddp_conv_dense2x2_set(int on);
 void ddp_conv_tune_clear();
 void ddp_conv_force_tile(int tile_plus_one, int stages);
+#ifdef DDP_CONV_STAMPS
+// diagnostic builds only (common.h ConvStampBuf): where the conv GEMM launches record their
+// per-item cycle stamps; ``buf`` = 4 + 4 * cap zeroed 32-bit words on the device, or null
+void ddp_conv_stamps_set(void* buf, int cap);
+#endif
 int ddp_pack_conv_weights(const ddp_amd::PackDesc* descs, int n, hipStream_t st);
 // ``sched``: learning rate from the device table; ``sched_advance`` = 1: this launch ends the
 // training step and stages the table's next step (LrSched::next = step + 1)

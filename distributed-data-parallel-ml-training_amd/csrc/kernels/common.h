@@ -147,6 +147,60 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// x / d for 0 <= x < 2^31 with a multiplier precomputed on the host (make_fastdiv, d >= 1):
+// q = (mulhi(x, mul) + x) >> sh. Every divisor that is fixed for a launch travels as one of
+// these in the kernel arguments: a runtime integer division is a 30-40 instruction software
+// routine on this ISA, a FastDiv is a multiply-high, an add and a shift — scalar instructions
+// when x is uniform over the wave.
+struct FastDiv {
+  unsigned mul;
+  int sh;
+};
+__device__ __forceinline__ int fast_div(int x, FastDiv d) {
+  return (int)((__umulhi((unsigned)x, d.mul) + (unsigned)x) >> d.sh);
+}
+inline FastDiv make_fastdiv(int d) {
+  FastDiv f;
+  int sh = 0;
+  while ((1ll << sh) < d) ++sh;
+  f.sh = sh;
+  f.mul = (unsigned)((((1ull << sh) - (unsigned long long)d) << 32) / (unsigned long long)d + 1);
+  return f;
+}
+
+// In-kernel cycle stamps of the conv GEMM work items — diagnostic builds only
+// (-DDDP_CONV_STAMPS, _build.py variant "stamps"; tools/probes/conv_item_stamps.py). The shipped
+// builds compile none of this. A stamped kernel records, per work item, the shader-clock cycles
+// its first wave spent in setup (index math, gather state), in the k-loop (prologue DMA
+// included) and in the epilogue. Buffer: word 0 counts the records, word 4 + 4 i.. holds record
+// i = {tag, setup, k-loop, epilogue}; records past ``cap`` are counted but not written.
+#ifdef DDP_CONV_STAMPS
+struct ConvStampBuf {
+  unsigned* buf;
+  int cap;
+};
+extern ConvStampBuf g_conv_stamps;  // host: the buffer the next launches record into (or null)
+__device__ __forceinline__ unsigned long long stamp_now() {
+  // the scheduling barriers pin the read between the phases it separates
+  __builtin_amdgcn_sched_barrier(0);
+  const unsigned long long t = __builtin_readcyclecounter();
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+__device__ __forceinline__ void stamp_put(const ConvStampBuf& s, unsigned tag, unsigned long long t0,
+                                          unsigned long long t1, unsigned long long t2,
+                                          unsigned long long t3) {
+  if (!s.buf || threadIdx.x != 0) return;
+  const unsigned i = atomicAdd(s.buf, 1u);
+  if (i >= (unsigned)s.cap) return;
+  unsigned* r = s.buf + 4 + 4 * (size_t)i;
+  r[0] = tag;
+  r[1] = (unsigned)(t1 - t0);
+  r[2] = (unsigned)(t2 - t1);
+  r[3] = (unsigned)(t3 - t2);
+}
+#endif
+
 // Counter-based RNG (splitmix-style 32-bit hash); identical formula in data/synthetic.py.
 __host__ __device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du;

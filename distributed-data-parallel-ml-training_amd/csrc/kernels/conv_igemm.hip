@@ -53,14 +53,7 @@ typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef short short8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
 
-// x / d for 0 <= x < 2^31 with a precomputed multiplier (d >= 1):  q = (mulhi(x, mul) + x) >> sh
-struct FastDiv {
-  unsigned mul;
-  int sh;
-};
-__device__ __forceinline__ int fast_div(int x, FastDiv d) {
-  return (int)((__umulhi((unsigned)x, d.mul) + (unsigned)x) >> d.sh);
-}
+// (FastDiv / fast_div / make_fastdiv: common.h)
 // zero n16 16-byte chunks (the strided dgrad's untouched phases; see conv_dgrad_impl)
 __global__ __launch_bounds__(256) void zero16_kernel(uint4* __restrict__ p, size_t n16) {
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256)
@@ -146,6 +139,17 @@ struct ConvArgs {
   // are a 32-bit mask); ddp_conv_rows_pm_set picks the images (<= 64 pixels or any, all convs
   // or R*S > 1 only).
   int pixmajor;
+  // Every divisor of the per-item index math that is fixed for the launch (prepare_cfg): tiles
+  // per split, column tiles, images (pixel-major rows), the reduction's channel dim (FWD C,
+  // DGRAD K) and its 64-channel blocks, taps per kernel row of the reduction index (phase: St),
+  // S, C, 64-image blocks, the dense 2x2 form's C and K, the split count. A work item is short
+  // (a 2x2-layer item runs 64 MFMAs per wave), and each runtime division it replaced was a
+  // 30-40 instruction routine paid again by every item.
+  FastDiv dTiles, dTilesN, dN, dCdim, dKb, dSdec, dS, dC, dNb, dD2C, dD2K, dSplits;
+  int w_dq, w_dp;            // WGRAD "same" conv: (q, p) advance of a reduction row per k-step
+#ifdef DDP_CONV_STAMPS
+  ConvStampBuf stamps;       // diagnostic builds: per-item cycle stamps (common.h)
+#endif
 };
 
 // the accumulating DGRAD's first-branch value of 4 / 8 consecutive channels starting at flat
@@ -350,8 +354,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
   int wp[CB], wq[CB];
   int w_rr = 0, w_ss = 0, w_lim = 0;  // tap offsets r - pad, s - pad; b_off bound (m < Kg)
   const bool wsame = MODE == MODE_WGRAD && gg.stride == 1 && gg.P == gg.H && gg.Q == gg.W;
-  const int w_dq = wsame ? BK % gg.Q : 0;                 // q advance per k-step
-  const int w_dp = wsame ? (BK / gg.Q) % gg.P : 0;        // p advance per k-step (mod P)
+  const int w_dq = args.w_dq;                             // q advance per k-step: BK % Q
+  const int w_dp = args.w_dp;                             // p advance per k-step: (BK / Q) % P
   const int w_dm = wsame ? 2 * BK * gg.C : 0;             // byte advance per k-step
   // pixel-major WGRAD (ConvArgs::pixmajor): the k-step's (image block n0, pixel pq) and the
   // tile's tap (pm_r, pm_s), all uniform; the pixels the tap keeps inside the image are the
@@ -361,6 +365,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
   // valid taps and the k-step's tap
   const bool pmr = MODE != MODE_WGRAD && args.pixmajor;
   int pmr_pq = 0, pmr_n0 = 0, pmr_row0 = 0, pmr_t = 0;
+  int pmr_pp = 0, pmr_qq = 0;  // the pixel's (p, q), decomposed once per item
   unsigned pmr_mask = 0;
   int pm_p = 0, pm_q = 0, pm_qlo = 0, pm_qhi = 0, pm_n0 = 0, pm_r = 0, pm_s = 0;
   int row0 = 0, col0 = 0, zsplit = 0, ks_begin = 0, ks_end = 0, cur_tile = 0;
@@ -382,13 +387,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
   const __amdgpu_buffer_rsrc_t rsB = make_rsrc(args.b, args.b_bytes);
 
   auto setup = [&](int item) {
-    zsplit = item / tiles;
+    // (every division below by a launch constant is a host-precomputed FastDiv: ConvArgs)
+    zsplit = fast_div(item, args.dTiles);
     const int tile = xcd_remap(item - zsplit * tiles, tiles);
     cur_tile = tile;
     // column tiles fastest: the run of consecutive tiles xcd_remap gives one XCD shares an
     // A-row slice in its L2 (row-tiles-fastest measured slower: VGG-11 b256 0.854 vs 0.835 ms,
     // ResNet-50 26.84 vs 26.41 ms, same box; tools/gpu/r4m.sh)
-    const int tm = tile / tiles_n;
+    const int tm = fast_div(tile, args.dTilesN);
     const int tn = tile - tm * tiles_n;
     row0 = tm * BM;
     col0 = tn * BN;
@@ -397,9 +403,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
     if (MODE != MODE_WGRAD) {
       if (pmr) {
         // row (pq, n): the tile's pixel and images; per chunk only the row's image stride
-        pmr_pq = row0 / gg.N;
+        pmr_pq = fast_div(row0, args.dN);
         pmr_n0 = row0 - pmr_pq * gg.N;
         pmr_row0 = row0;
+        pmr_pp = fast_div(pmr_pq, args.dQ);  // (dQ divides by Q == W here: rows_pixmajor_ok)
+        pmr_qq = pmr_pq - pmr_pp * gg.Q;
         const int img = MODE == MODE_FWD ? gg.H * gg.W * gg.C : gg.P * gg.Q * gg.K;
 #pragma unroll
         for (int i = 0; i < CA; ++i) a_off[i] = 2 * (((tid >> 3) + 32 * i) * img + lcA * 8);
@@ -416,7 +424,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
       }
       if (MODE == MODE_FWD && args.d2x2) {
         // dense 2x2: column (p, q, k) reads Wc row k; the tap follows (p, q) and the k-step
-        d2pos = col0 / args.d2K;
+        d2pos = fast_div(col0, args.dD2K);
 #pragma unroll
         for (int i = 0; i < CB; ++i) {
           const int col = col0 + (tid >> 3) + 32 * i;
@@ -432,7 +440,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
       } else if (args.d2x2) {
         // dense 2x2 DGRAD: column (h, w, c) = channel c of Wc rows k (the k-step's reduction
         // rows (p, q, k)), tap from (h, w) and the k-step's (p, q)
-        d2pos = col0 / args.d2C;
+        d2pos = fast_div(col0, args.dD2C);
 #pragma unroll
         for (int i = 0; i < CB; ++i) {
           const int col = col0 + (lcB ^ swz_row_step<BN>(i)) * 8;
@@ -453,7 +461,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
       if (pmr) {
         // the taps that keep the tile's pixel inside the image; this split's share of their
         // k-steps; the first one's tap and channel block
-        const int pp = pmr_pq / gg.Q, qq = pmr_pq - pp * gg.Q, kb = cdim / BK;
+        const int pp = pmr_pp, qq = pmr_qq, kb = cdim / BK;
         unsigned m = 0;
         for (int r = 0; r < gg.R; ++r)
           for (int s2 = 0; s2 < gg.S; ++s2) {
@@ -464,22 +472,23 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
           }
         pmr_mask = m;
         const int V = __builtin_popcount(m) * kb;
-        const int per = (V + args.splits - 1) / args.splits;
+        const int per = fast_div(V + args.splits - 1, args.dSplits);
         ks_begin = min(V, zsplit * per);
         ks_end = min(V, ks_begin + per);
-        int jv = ks_begin / kb;
+        const int jv0 = fast_div(ks_begin, args.dKb);
+        int jv = jv0;
         unsigned mm = m;
         for (; jv > 0 && mm; --jv) mm &= mm - 1;
         pmr_t = mm ? __builtin_ctz(mm) : 0;
-        kc = (ks_begin - (ks_begin / kb) * kb) * BK;
-        kr = pmr_t / gg.S;
+        kc = (ks_begin - jv0 * kb) * BK;
+        kr = fast_div(pmr_t, args.dS);
         ks_ = pmr_t - kr * gg.S;
       } else {
         // decomposition of the first reduction index (fast: of the k-step; slow: of the chunk)
         const int kk = ks_begin * BK + (fast ? 0 : lcA * 8);
-        const int rs = kk / cdim;
+        const int rs = fast_div(kk, args.dCdim);
         kc = kk - rs * cdim;
-        kr = rs / Sdec;
+        kr = fast_div(rs, args.dSdec);
         ks_ = rs - kr * Sdec;
       }
     } else {
@@ -490,15 +499,15 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
         a_off[i] = kout < args.Mg ? 2 * (((tid + i * 256) / NCA) * gg.K + kout) : (int)kOOB;
       }
       const int j = col0 + lcB * 8;
-      const int rs = j / gg.C;
+      const int rs = fast_div(j, args.dC);
       xk.c = j - rs * gg.C;
-      xk.r = rs / gg.S;
+      xk.r = fast_div(rs, args.dS);
       xk.s = rs - xk.r * gg.S;
       xk.ok = j < args.Ng;
       if (pm) {
         // one tap per column tile: its valid pixels, this split's share of the valid k-steps
-        const int t = col0 / gg.C;
-        pm_r = t / gg.S;
+        const int t = fast_div(col0, args.dC);
+        pm_r = fast_div(t, args.dS);
         pm_s = t - pm_r * gg.S;
         // the pixels (p, q) with (p + r - pad, q + s - pad) inside the image: a rectangle
         const int PQ = gg.P * gg.Q, nb = gg.N / BK;
@@ -507,13 +516,16 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
         pm_qhi = min(gg.Q, gg.W + gg.pad - pm_s);
         const int nq = max(0, pm_qhi - pm_qlo);
         const int V = max(0, p_hi - p_lo) * nq * nb;
-        const int per = (V + args.splits - 1) / args.splits;
+        const int per = fast_div(V + args.splits - 1, args.dSplits);
         ks_begin = min(V, zsplit * per);
         ks_end = min(V, ks_begin + per);
-        // the first k-step's pixel: the (ks_begin / nb)-th of the rectangle, row-major
-        const int jv = ks_begin / nb;
-        pm_p = p_lo + (nq ? jv / nq : 0);
-        pm_q = pm_qlo + (nq ? jv - (jv / nq) * nq : 0);
+        // the first k-step's pixel: the (ks_begin / nb)-th of the rectangle, row-major (nq is
+        // the tap's own row length, not a launch constant: the one runtime division left, on
+        // scalar values)
+        const int jv = fast_div(ks_begin, args.dNb);
+        const int jp = nq ? jv / nq : 0;
+        pm_p = p_lo + jp;
+        pm_q = pm_qlo + (nq ? jv - jp * nq : 0);
         pm_n0 = (ks_begin - jv * nb) * BK;
         constexpr int NCA = BM / 8;
         constexpr int NCB = BN / 8;
@@ -537,8 +549,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
 #pragma unroll
         for (int i = 0; i < CB; ++i) {
           const int m = ks_begin * BK + (tid + i * 256) / NCB;
-          const int rem = m % pq;
-          wp[i] = rem / gg.Q;
+          const int rem = m - fast_div(m, args.dPQ) * pq;  // (WGRAD: dPQ, dQ divide by P*Q, Q)
+          wp[i] = fast_div(rem, args.dQ);
           wq[i] = rem - wp[i] * gg.Q;
           b_off[i] = m * (2 * gg.C) + xk_same;
         }
@@ -552,7 +564,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
     unsigned short* Bs = As + TILE_A;
     const int k0 = ks * BK;
     if (MODE != MODE_WGRAD && pmr) {
-      const int pp = pmr_pq / gg.Q, qq = pmr_pq - pp * gg.Q;
+      const int pp = pmr_pp, qq = pmr_qq;
       const int hh = MODE == MODE_FWD ? pp + kr - gg.pad : pp - kr + gg.pad;
       const int ww = MODE == MODE_FWD ? qq + ks_ - gg.pad : qq - ks_ + gg.pad;
       const int sa = MODE == MODE_FWD ? 2 * (((pmr_n0 * gg.H + hh) * gg.W + ww) * cdim + kc)
@@ -568,7 +580,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
         kc = 0;
         const unsigned rest = pmr_mask & ~((2u << pmr_t) - 1u);
         pmr_t = rest ? __builtin_ctz(rest) : pmr_t;
-        kr = pmr_t / gg.S;
+        kr = fast_div(pmr_t, args.dS);
         ks_ = pmr_t - kr * gg.S;
       }
     } else if (MODE != MODE_WGRAD) {
@@ -589,7 +601,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
         if (args.d2x2) {
           // FWD: k-step = input pixel hw, channels c0..; DGRAD: k-step = output pixel pq,
           // channels k0..; the column tile fixed the other pixel (d2pos)
-          const int pix = MODE == MODE_FWD ? kc / args.d2C : kc / args.d2K;
+          const int pix = fast_div(kc, MODE == MODE_FWD ? args.dD2C : args.dD2K);
           const int ch = kc - pix * (MODE == MODE_FWD ? args.d2C : args.d2K);
           const int pq = MODE == MODE_FWD ? d2pos : pix, hw = MODE == MODE_FWD ? pix : d2pos;
           const int tap = ((hw >> 1) - (pq >> 1) + 1) * 3 + ((hw & 1) - (pq & 1) + 1);
@@ -631,8 +643,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
           for (int i = 0; i < CB; ++i) {
             const int m = (tid + i * 256) / (BN / 8);
             const int kkr = k0 + m;
-            const int tap = kkr / gg.K, kout = kkr - tap * gg.K;
-            const int tr = tap / Sdec, ts = tap - tr * Sdec;
+            const int tap = fast_div(kkr, args.dCdim), kout = kkr - tap * gg.K;  // (cdim = K)
+            const int tr = fast_div(tap, args.dSdec), ts = tap - tr * Sdec;
             const int rr = phase ? args.r0 + gg.stride * tr : tr, ss = phase ? args.s0 + gg.stride * ts : ts;
             const int off = b_off[i] - 2 * m * RSC + 2 * ((kout * gg.R * gg.S + rr * gg.S + ss) * gg.C);
             dma_buf(rsB, (kkr < args.Kg && b_off[i] != (int)kOOB) ? off : (int)kOOB,
@@ -1061,8 +1073,47 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
     }
     int wrs = 0, wc = 0;
     if (MODE == MODE_WGRAD) {  // GEMM column -> (r*S + s, c); c..c+3 share the tap
-      wrs = col / g.C;
+      wrs = fast_div(col, args.dC);
       wc = col - wrs * g.C;
+    }
+    if (MODE == MODE_WGRAD && !split && g.wkrsc && g.Creal == g.C) {
+      // Whole gradient elements, updated in place (dW += v, or the fused SGD step on the master
+      // + momentum, ConvArgs::sgd): every load of the column goes out before its first store.
+      // Interleaved per row, each load queued behind the previous row's store — the compiler
+      // cannot prove they do not alias — so the epilogue paid TM memory round trips in series:
+      // 37 % of a 2x2-layer WGRAD item's lifetime at b256, 65 % at b32
+      // (profiles/conv_item_overhead.md). Same values, same operations, same order per element.
+      const bool sgd = SGDM && args.sgd.p;
+      float* const pb = sgd ? args.sgd.p : args.dw;
+      size_t e[TM];
+      bool ok[TM];
+      float4 pv[TM], bv[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int row = row0 + wm * WTM + i * 16 + rl;
+        ok[i] = cok && row < args.Mg;
+        e[i] = ((size_t)row * g.R * g.S + wrs) * g.C + wc;
+        if (!ok[i]) continue;
+        pv[i] = *reinterpret_cast<const float4*>(pb + e[i]);
+        if (sgd) bv[i] = *reinterpret_cast<const float4*>(args.sgd.buf + e[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        if (!ok[i]) continue;
+        const f32x4 v = acc[i][j];
+        if (sgd) {
+          const SgdFuse& h = args.sgd;
+          pv[i].x = sgd_update1(pv[i].x, v[0], bv[i].x, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv[i].y = sgd_update1(pv[i].y, v[1], bv[i].y, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv[i].z = sgd_update1(pv[i].z, v[2], bv[i].z, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          pv[i].w = sgd_update1(pv[i].w, v[3], bv[i].w, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
+          *reinterpret_cast<float4*>(args.sgd.buf + e[i]) = bv[i];
+        } else {
+          pv[i].x += v[0]; pv[i].y += v[1]; pv[i].z += v[2]; pv[i].w += v[3];
+        }
+        *reinterpret_cast<float4*>(pb + e[i]) = pv[i];
+      }
+      continue;
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -1070,30 +1121,13 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
       if (!cok || row >= args.Mg) continue;
       const f32x4 v = acc[i][j];
       if (MODE == MODE_WGRAD && !split) {
-        if (SGDM && g.wkrsc && g.Creal == g.C && args.sgd.p) {  // master-only SGD (ConvArgs::sgd)
-          const size_t e = ((size_t)row * g.R * g.S + wrs) * g.C + wc;
-          float4 pv = *reinterpret_cast<const float4*>(args.sgd.p + e);
-          float4 bv = *reinterpret_cast<const float4*>(args.sgd.buf + e);
-          const SgdFuse& h = args.sgd;
-          pv.x = sgd_update1(pv.x, v[0], bv.x, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          pv.y = sgd_update1(pv.y, v[1], bv.y, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          pv.z = sgd_update1(pv.z, v[2], bv.z, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          pv.w = sgd_update1(pv.w, v[3], bv.w, sgd_lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
-          *reinterpret_cast<float4*>(args.sgd.p + e) = pv;
-          *reinterpret_cast<float4*>(args.sgd.buf + e) = bv;
-        } else if (g.wkrsc && g.Creal == g.C) {
-          float* d = args.dw + ((size_t)row * g.R * g.S + wrs) * g.C + wc;
-          float4 o = *reinterpret_cast<float4*>(d);
-          o.x += v[0]; o.y += v[1]; o.z += v[2]; o.w += v[3];
-          *reinterpret_cast<float4*>(d) = o;
-        } else {
+        // (the [K][R][S][C] layout with unpadded channels took the vector path above)
 #pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if (wc + t >= g.Creal) break;
-            const size_t di = g.wkrsc ? ((size_t)row * g.R * g.S + wrs) * g.Creal + wc + t
-                                      : ((size_t)row * g.Creal + wc + t) * g.R * g.S + wrs;
-            args.dw[di] += v[t];
-          }
+        for (int t = 0; t < 4; ++t) {
+          if (wc + t >= g.Creal) break;
+          const size_t di = g.wkrsc ? ((size_t)row * g.R * g.S + wrs) * g.Creal + wc + t
+                                    : ((size_t)row * g.Creal + wc + t) * g.R * g.S + wrs;
+          args.dw[di] += v[t];
         }
       } else if (split) {
         // (pixel-major rows: the slab takes the NHWC row, so every finish kernel is unchanged)
@@ -1214,12 +1248,20 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
   // NST-stage LDS ring: the DMAs of up to NST-1 k-steps are in flight while one is computed.
   constexpr int DMA = CA + CB;  // vector-memory instructions per thread per stage
   for (int item = bid; item < nitems; item += nblk) {
+#ifdef DDP_CONV_STAMPS
+    const unsigned long long st0 = stamp_now();
+#endif
     setup(item);
+#ifdef DDP_CONV_STAMPS
+    const unsigned long long st1 = stamp_now();
+#endif
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int kb = ks_begin, ke = ks_end;  // host guarantees kb < ke for every item
+    // kb == ke is legal: a pixel-major item whose share of the valid k-steps is empty (a corner
+    // pixel keeps 4 of 9 taps) runs no k-step and stores a zero tile / zero slab
+    const int kb = ks_begin, ke = ks_end;
 #pragma unroll
     for (int s = 0; s < NST - 1; ++s)
       if (kb + s < ke) issue(kb + s, s);
@@ -1241,7 +1283,13 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& args, unsigned s
       mma(fa1, fb1);
       stage = stage + 1 == NST ? 0 : stage + 1;
     }
+#ifdef DDP_CONV_STAMPS
+    const unsigned long long st2 = stamp_now();
+#endif
     epilogue(row0, col0, zsplit, args.splits > 1);
+#ifdef DDP_CONV_STAMPS
+    stamp_put(args.stamps, (unsigned)MODE, st0, st1, st2, stamp_now());
+#endif
     // all reads of the ring done before the next item's prologue DMA. Not after the last item:
     // vmcnt also counts the epilogue's stores, and waiting for their acknowledgement would hold
     // the workgroup slot (and its registers) for a full memory round trip after the last MFMA
@@ -2015,14 +2063,16 @@ __global__ __launch_bounds__(256) void bwd_pair_finish_kernel(FinishArgs fa, int
 // ------------------------------- host launcher -------------------------------
 using namespace ddp_amd;
 
-static FastDiv make_fastdiv(int d) {
-  FastDiv f;
-  int sh = 0;
-  while ((1ll << sh) < d) ++sh;
-  f.sh = sh;
-  f.mul = (unsigned)((((1ull << sh) - (unsigned long long)d) << 32) / (unsigned long long)d + 1);
-  return f;
+#ifdef DDP_CONV_STAMPS
+namespace ddp_amd {
+ConvStampBuf g_conv_stamps{nullptr, 0};
 }
+// diagnostic builds: the conv GEMM launches that follow record their per-item cycle stamps into
+// ``buf`` (4 + 4 * cap 32-bit words, zeroed by the caller; common.h); null switches them off
+extern "C" void ddp_conv_stamps_set(void* buf, int cap) {
+  g_conv_stamps = ConvStampBuf{(unsigned*)buf, buf ? std::max(0, cap) : 0};
+}
+#endif
 
 static bool fits_buffer(size_t elems) { return elems * 2 < (size_t)kOOB; }
 
@@ -2183,6 +2233,28 @@ static int prepare_cfg(ConvArgs& a, int splits) {
     a.dPQ = make_fastdiv(std::max(1, a.g.P * a.g.Q));
     a.dQ = make_fastdiv(std::max(1, a.g.Q));
   }
+  {
+    const ConvGeom& g = a.g;
+    const int cdim = MODE == MODE_FWD ? g.C : g.K;
+    const bool wsame = MODE == MODE_WGRAD && g.stride == 1 && g.P == g.H && g.Q == g.W;
+    a.dTiles = make_fastdiv(std::max(1, tiles));
+    a.dTilesN = make_fastdiv(std::max(1, (a.Ng + BN - 1) / BN));
+    a.dN = make_fastdiv(std::max(1, g.N));
+    a.dCdim = make_fastdiv(std::max(1, cdim));
+    a.dKb = make_fastdiv(std::max(1, cdim / BK));
+    a.dSdec = make_fastdiv(std::max(1, MODE == MODE_DGRAD && a.phase ? a.St : g.S));
+    a.dS = make_fastdiv(std::max(1, g.S));
+    a.dC = make_fastdiv(std::max(1, g.C));
+    a.dNb = make_fastdiv(std::max(1, g.N / BK));
+    a.dD2C = make_fastdiv(std::max(1, a.d2C));
+    a.dD2K = make_fastdiv(std::max(1, a.d2K));
+    a.dSplits = make_fastdiv(splits);
+    a.w_dq = wsame ? BK % g.Q : 0;
+    a.w_dp = wsame ? (BK / g.Q) % g.P : 0;
+  }
+#ifdef DDP_CONV_STAMPS
+  a.stamps = g_conv_stamps;
+#endif
   return tiles * splits;
 }
 
@@ -2428,10 +2500,16 @@ constexpr int kNumTiles = 8;
 // the 256-wide k-major tiles put odd DMA chunks in the wrong swizzled LDS slot — DGRAD 64x256 /
 // 128x256 computed a wrong dx, WGRAD 256x64 / 256x128 a wrong dW; tests/test_gpu_kernels.py
 // ::test_conv_every_tile now checks every tile in every mode.)
+// The dense 2x2 form takes one tap per column tile (ConvArgs::d2x2: d2pos), so its column tile
+// must lie inside one pixel's channel block: BN divides K (FWD) / C (DGRAD). 64-wide tiles
+// always do (dense2x2_ok).
+static const int kTileBN[kNumTiles] = {128, 64, 128, 64, 64, 256, 128, 256};
 template <int MODE>
-static bool tile_ok(int tile) {
+static bool tile_ok(int tile, const ConvArgs& a) {
+  if (tile < 0 || tile >= kNumTiles) return false;
   if (MODE == MODE_WGRAD && (tile == 5 || tile == 7)) return false;
-  return tile >= 0 && tile < kNumTiles;
+  if (MODE != MODE_WGRAD && a.d2x2 && (MODE == MODE_FWD ? a.d2K : a.d2C) % kTileBN[tile]) return false;
+  return true;
 }
 
 // tile / split-K / LDS-stage choice for a problem: the measured table, else the cost model
@@ -2440,10 +2518,10 @@ template <int MODE>
 static void plan_mode(ConvArgs& a, size_t ws_elems, int* best_out, int* sp, int* nst_out) {
   const double c[4] = {tile_cost(128, 128, a, ws_elems, &sp[0]), tile_cost(128, 64, a, ws_elems, &sp[1]),
                        tile_cost(64, 128, a, ws_elems, &sp[2]), tile_cost(64, 64, a, ws_elems, &sp[3])};
-  int best = 0, nst = g_force_stages;
-  for (int i = 1; i < 4; ++i)
-    if (c[i] < c[best]) best = i;
-  if (g_force_tile >= 1 && g_force_tile <= kNumTiles && tile_ok<MODE>(g_force_tile - 1)) {
+  int best = 3, nst = g_force_stages;  // (64x64 serves every problem)
+  for (int i = 2; i >= 0; --i)
+    if (tile_ok<MODE>(i, a) && c[i] <= c[best]) best = i;
+  if (g_force_tile >= 1 && g_force_tile <= kNumTiles && tile_ok<MODE>(g_force_tile - 1, a)) {
     best = g_force_tile - 1;
     if (best >= 4) {
       static const int bmn[4][2] = {{256, 64}, {64, 256}, {256, 128}, {128, 256}};
@@ -2451,7 +2529,7 @@ static void plan_mode(ConvArgs& a, size_t ws_elems, int* best_out, int* sp, int*
     }
   } else if (a.splits <= 0) {
     auto it = g_tuned.find(TuneKey{MODE, a.Mg, a.Ng, a.Kg});
-    if (it != g_tuned.end() && tile_ok<MODE>(it->second.tile)) {
+    if (it != g_tuned.end() && tile_ok<MODE>(it->second.tile, a)) {
       const size_t slab = (size_t)a.Mg * a.Ng;
       const int ksteps = (a.Kg + 63) / 64;
       int spl = std::max(1, std::min(it->second.splits, ksteps));

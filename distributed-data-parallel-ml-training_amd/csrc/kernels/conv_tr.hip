@@ -114,6 +114,13 @@ struct Args {
   float* in_coef;            // [6][C]: scale, shift, mean, invstd (written by block 0)
   unsigned short* y_out;     // [N][H][W][C]
   int z_bytes;
+  // the launch-constant divisors of the per-block index math (common.h FastDiv): tiles per
+  // split, column tiles, bands per image, stored pixels per image (rows + 2) * W, W, output
+  // pixels per image in a tile rows * W
+  FastDiv dTiles, dTilesN, dBands, dPw, dW, dPerImg;
+#ifdef DDP_CONV_STAMPS
+  ConvStampBuf stamps;       // diagnostic builds: per-item cycle stamps (common.h)
+#endif
 };
 
 template <int BM, int BN, int NST, int NL, int IN>
@@ -140,20 +147,26 @@ void conv_tr_fwd_kernel(Args a) {
   const int wm = wid >> 1, wn = wid & 1;
   const int W = a.W, H = a.H, C = a.C, K = a.K;
   const int M = a.N * H * W;
+#ifdef DDP_CONV_STAMPS
+  // setup = everything before the first patch load (fused input: the BatchNorm fold included);
+  // tag 3 (conv_igemm.hip's kernels record their MODE, 0..2)
+  const unsigned long long st0 = stamp_now();
+#endif
   const int ncb = C / 64;
 
   const int tiles = a.tiles_m * a.tiles_n;
   const int item = blockIdx.x;
-  const int sp = item / tiles;
+  const int sp = fast_div(item, a.dTiles);
   const int tile = xcd_remap(item - sp * tiles, tiles);
-  const int tm = tile / a.tiles_n;  // column tiles fastest (as conv_igemm.hip)
+  const int tm = fast_div(tile, a.dTilesN);  // column tiles fastest (as conv_igemm.hip)
   const int tn = tile - tm * a.tiles_n;
   const int row0 = tm * BM, col0 = tn * BN;
   const int cb0 = sp * a.cbps, cb1 = min(ncb, cb0 + a.cbps);
   const int nsteps = (cb1 - cb0) * 9;
   // tile -> images / band
-  const int n0 = (tm / a.bands) * a.imgs;
-  const int h0 = (tm % a.bands) * a.rows;  // first output row of the band
+  const int tband = fast_div(tm, a.dBands);
+  const int n0 = tband * a.imgs;
+  const int h0 = (tm - tband * a.bands) * a.rows;  // first output row of the band
 
   const __amdgpu_buffer_rsrc_t rsA = IN ? make_rsrc(a.zin, a.z_bytes) : make_rsrc(a.x, a.x_bytes);
   if (BNIN) {
@@ -202,8 +215,8 @@ void conv_tr_fwd_kernel(Args a) {
       unsigned off = kOOB;
       int dst = -1, yd = -1;
       if (px < npix) {
-        const int img = px / pw, loc = px - img * pw;
-        const int hr = loc / W, wc = loc - hr * W;
+        const int img = fast_div(px, a.dPw), loc = px - img * pw;
+        const int hr = fast_div(loc, a.dW), wc = loc - hr * W;
         const int h = h0 + hr - 1;
         if (h >= 0 && h < H) {
           const int n = n0 + img;
@@ -300,8 +313,8 @@ void conv_tr_fwd_kernel(Args a) {
   for (int i = 0; i < TM; ++i) {
     const int m = wm * WTM + i * 16 + (lane & 15);  // tile-local output row
     const int per_img = a.rows * W;
-    const int img = m / per_img, rem = m - img * per_img;
-    const int rr = rem / W, cc = rem - rr * W;
+    const int img = fast_div(m, a.dPerImg), rem = m - img * per_img;
+    const int rr = fast_div(rem, a.dW), cc = rem - rr * W;
     const int pix = img * a.imgp + rr * W + cc;  // patch pixel at tap row 0, column cc
     fa_base[i] = (plane_base(lane >> 4, a.plane) + pix) * 16;
     col_ok[i] = (cc >= 1 ? 1u : 0u) | (cc <= W - 2 ? 2u : 0u);
@@ -346,6 +359,9 @@ void conv_tr_fwd_kernel(Args a) {
   };
 
   // ---- prologue: patch of cb0 (through registers), B k-steps 0 .. NST-2
+#ifdef DDP_CONV_STAMPS
+  const unsigned long long st1 = stamp_now();
+#endif
   load_a(cb0);
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s)
@@ -381,6 +397,12 @@ void conv_tr_fwd_kernel(Args a) {
   }
 
   // ---- epilogue: acc[i][j][v] = D[row0 + wm*WTM + i*16 + (lane&15)][col0 + wn*WTN + j*16 + 4*(lane>>4) + v]
+#ifdef DDP_CONV_STAMPS
+  const unsigned long long st2 = stamp_now();
+#define DDP_TR_STAMP_END() stamp_put(a.stamps, 3u, st0, st1, st2, stamp_now())
+#else
+#define DDP_TR_STAMP_END() ((void)0)
+#endif
   const int rl = lane & 15, cq = 4 * (lane >> 4);
   const int cbase = col0 + wn * WTN + cq;
   if (a.splits > 1) {
@@ -397,6 +419,7 @@ void conv_tr_fwd_kernel(Args a) {
         *reinterpret_cast<float4*>(slab + (size_t)row * K + col) = (float4){v[0], v[1], v[2], v[3]};
       }
     }
+    DDP_TR_STAMP_END();
     return;
   }
   const bool red = a.stats != nullptr;
@@ -440,7 +463,10 @@ void conv_tr_fwd_kernel(Args a) {
       }
     }
   }
-  if (!red) return;
+  if (!red) {
+    DDP_TR_STAMP_END();
+    return;
+  }
   __syncthreads();
   if (wm == 0 && rl == 0) {
     float* st = a.stats + stat_rep(blockIdx.x) * 2 * K;
@@ -457,6 +483,7 @@ void conv_tr_fwd_kernel(Args a) {
       }
     }
   }
+  DDP_TR_STAMP_END();
 }
 
 // ------------------------------------------------------------------ host side
@@ -729,6 +756,12 @@ extern "C" int ddp_conv_fwd_tr(const ConvGeom* g, const void* x, const void* wc,
   a.abuf_elems = geo.abuf;
   a.tiles_m = (int)(M / c.bm);
   a.tiles_n = K / c.bn;
+  a.dTiles = make_fastdiv(std::max(1, a.tiles_m * a.tiles_n));
+  a.dTilesN = make_fastdiv(std::max(1, a.tiles_n));
+  a.dBands = make_fastdiv(std::max(1, geo.bands));
+  a.dPw = make_fastdiv((geo.rows + 2) * W);
+  a.dW = make_fastdiv(W);
+  a.dPerImg = make_fastdiv(geo.rows * W);
   if (in) {
     a.zin = (const unsigned short*)in->z;
     a.in_stats = in->stats;
@@ -740,6 +773,9 @@ extern "C" int ddp_conv_fwd_tr(const ConvGeom* g, const void* x, const void* wc,
     a.y_out = (unsigned short*)in->y;
     a.z_bytes = (int)(2 * M * C * (in->pool ? 4 : 1));
   }
+#ifdef DDP_CONV_STAMPS
+  a.stamps = g_conv_stamps;
+#endif
   const int items = a.tiles_m * a.tiles_n * pl.splits;
   if (!launch_stages(c, in_mode, a, geo.nl, items, st)) return 0;
   int e = (int)hipGetLastError();
