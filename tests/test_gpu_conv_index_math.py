@@ -9,11 +9,22 @@ tiles and split counts 1-3. Reference op: torch.nn.functional.conv2d in fp32 and
 backward. Tolerances are those of tests/test_gpu_kernels.py::test_conv_every_tile
 and test_conv_bwd_pair_forced_splits (relative l2 error < 1e-2: bf16 operands and outputs,
 fp32 accumulation).
+
+The norm alone passes over a local defect (one tile row, one tap of a corner pixel: see
+tests/test_exactness_cpu.py), so every comparison is also made per element against an fp64
+reference (tests/exactness.py assert_within) with the bound of an fp32-accumulated reduction of n
+terms stored with at most one bf16 rounding: 2**-8 |ref| + n * 2**-24 * sum |a b|, where n is
+the reduction length -- R*S*C + 1 (bias) for FWD z, K*R*S for DGRAD dx (both bf16), N*P*Q for
+WGRAD dw (fp32: no bf16 term). Where the output is bf16 the fp32 term carries the factor
+(1 + 2**-8) (exactness.dot_bound): the bf16 rounding acts on the value the kernel computed, not
+on the reference, so it is at most 2**-8 (|ref| + fp32 error) -- 0.4 % more on the small term than
+the formula above. tests/test_gpu_exact.py runs the same shapes on integers, bitwise.
 """
 import pytest
 import torch
 import torch.nn.functional as F
 
+from exactness import assert_within, dot_bound
 from test_gpu_kernels import DEV, _conv_setup, bf, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +44,34 @@ SHAPES = {
 _CACHE = {}
 
 
+def _ref64(x, w, b, dz, stride, pad):
+    """fp64 z, dx (NHWC) and dw of NCHW operands, and the same on the operands' magnitudes, as
+    (reference, bound) pairs for assert_within."""
+    def ops(x, w, b, dz):
+        xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        F.conv2d(xr, wr, None, stride, pad).backward(dz)
+        z = F.conv2d(x, w, b, stride, pad).permute(0, 2, 3, 1).contiguous()
+        return z, xr.grad.permute(0, 2, 3, 1).contiguous(), wr.grad
+    x, w, b, dz = (t.detach().double().cpu() for t in (x, w, b, dz))
+    ref, mag = ops(x, w, b, dz), ops(x.abs(), w.abs(), b.abs(), dz.abs())
+    K, C, R, S = w.shape
+    n = (R * S * C + 1, K * R * S, dz.shape[0] * dz.shape[2] * dz.shape[3])
+    return {k: (ref[i], dot_bound(ref[i], mag[i], n[i], 0 if k == "wgrad" else 1))
+            for i, k in enumerate(("fwd", "dgrad", "wgrad"))}
+
+
+def _elem_bad(bad, key, got, e64, names):
+    """The per-element check beside a rel_err: a failure is recorded in ``bad`` like the norm's."""
+    try:
+        worst = assert_within(got, e64[key][0], e64[key][1], names, what=key)
+        print(key, "worst |err| / bound", worst)
+    except AssertionError as e:
+        bad[key + " per element"] = str(e)
+
+
+NHWC, KCRS = ("n", "h", "w", "c"), ("k", "c", "r", "s")
+
+
 def _case(name):
     """Operands and fp32 references of a shape, computed once and shared (never modified)."""
     if name not in _CACHE:
@@ -48,7 +87,8 @@ def _case(name):
         wr = conv.weight.detach().clone().requires_grad_(True)
         F.conv2d(xr, wr, None, stride, pad).backward(dz)
         _CACHE[name] = dict(conv=conv, spec=spec, x=x, xn=xn, dz=dz, dzn=dzn, ref=ref,
-                            dx=xr.grad.permute(0, 2, 3, 1).contiguous(), dw=wr.grad)
+                            dx=xr.grad.permute(0, 2, 3, 1).contiguous(), dw=wr.grad,
+                            e64=_ref64(x, conv.weight, conv.bias, dz, stride, pad))
     return _CACHE[name]
 
 
@@ -87,6 +127,9 @@ def _separate(nat, name, splits, rows_pm=None, wgrad_pm=None):
     errs = {"fwd": rel_err(z, c["ref"]), "dgrad": rel_err(dx, c["dx"]), "wgrad": rel_err(dw, c["dw"])}
     print(name, splits, errs)
     bad = {k: v for k, v in errs.items() if not v < 1e-2}
+    _elem_bad(bad, "fwd", z, c["e64"], NHWC)
+    _elem_bad(bad, "dgrad", dx, c["e64"], NHWC)
+    _elem_bad(bad, "wgrad", dw, c["e64"], KCRS)
     if not _stats_ok(stats, z, K):
         bad["stats"] = "BatchNorm statistics of z"
     return bad
@@ -143,6 +186,8 @@ def test_pair_every_tile_and_split(native_ext, name, tile, sd, sw):
     errs = {"dgrad": rel_err(dx, c["dx"]), "wgrad": rel_err(dw, c["dw"])}
     print(name, tile, sd, sw, errs)
     bad = {k: v for k, v in errs.items() if not v < 1e-2}
+    _elem_bad(bad, "dgrad", dx, c["e64"], NHWC)
+    _elem_bad(bad, "wgrad", dw, c["e64"], KCRS)
     assert not bad, f"{name} pair tile {tile} splits {sd}/{sw}: {bad}"
 
 
@@ -166,6 +211,11 @@ def test_dense2x2_forward_and_pair(native_ext, dense):
     errs = {"fwd": rel_err(z, c["ref"]), "dgrad": rel_err(dx, c["dx"]), "wgrad": rel_err(dw, c["dw"])}
     print(dense, errs)
     assert not {k: v for k, v in errs.items() if not v < 1e-2}, errs
+    bad = {}
+    _elem_bad(bad, "fwd", z, c["e64"], NHWC)
+    _elem_bad(bad, "dgrad", dx, c["e64"], NHWC)
+    _elem_bad(bad, "wgrad", dw, c["e64"], KCRS)
+    assert not bad, bad
     assert _stats_ok(stats, z, K)
 
 
@@ -226,4 +276,8 @@ def test_tap_reuse_forward(native_ext, case, fused_in):
     err = rel_err(z, ref)
     print(case, fused_in, r, err)
     assert err < 1e-2
+    bad = {}
+    _elem_bad(bad, "fwd", z, _ref64(x, conv.weight, conv.bias, torch.zeros_like(ref).permute(
+        0, 3, 1, 2), 1, 1), NHWC)
+    assert not bad, bad
     assert _stats_ok(stats, z, K)
