@@ -21,35 +21,43 @@
 //                    dW[k][tap][c] += sum over the tile's pixels of dz * x, MFMA into fp32
 //                    accumulators that live across the wave's tiles -> one compact [64][28]
 //                    fp32 partial per block. dz, the layer's last full-resolution tensor
-//                    (33.5 MB at b256), is never stored: its only consumer was the weight
-//                    gradient GEMM, which read it back and left 512 slabs to a finish launch
+//                    (33.5 MB at b256), is never stored
 //   l0_wgrad_finish_kernel  fixed-order sum of the block partials, added into the gradient or
 //                    (registered SGD step, api.h SgdFuse) applied to the master weights
 //   l0_bwd_kernel<1> the dz pass that stores dz for the weight gradient GEMM (ops/layers.py
-//                    L0_WGRAD_FUSE = False; the fused variant's reference), l0_bwd_kernel<0> the
-//                    BN-backward sums through the recomputed z
-// Every pass runs the same conv code on the same inputs, so z is bit-identical to the forward's;
-// the arithmetic of each step is the one of conv_smallk.hip (conv) and bn_act.hip (finalize,
-// apply, first-maximum pool rule).
+//                    L0_WGRAD_FUSE = False; the fused variant's reference)
+// Every pass runs the same conv code (conv_z) on the same inputs, so z is bit-identical to the
+// forward's; the arithmetic of each step is the one of conv_smallk.hip (conv) and bn_act.hip
+// (finalize, apply, first-maximum pool rule).
 //
-// Tiling: a wave owns 16 output pixels = 2 image rows x 8 columns (four whole 2x2 pool windows)
-// x 64 channels: the conv is conv_smallk.hip's direct MFMA (lane = one pixel x 4 channels per
-// 16-channel tile, weights read from an LDS image staged once per block), and a pool window's
-// four values sit in lanes {l, l^1, l^8, l^9} of the same 16-lane row — max and argmax are
-// exchanged with DPP (quad_perm, row_ror:8), no LDS.
-// Measured (profiles/r4k_vgg11_b256_l0v5.md): 12.0 + 19.1 us forward, 15.3 + 17.3 us backward
-// at b256 against ~66 us of conv + BN passes unfused; step 0.835-0.846 vs 0.855 ms same box.
-//
-// Fused weight gradient (l0_bwd_kernel<2>): the conv contracts over (tap, channel) with lane =
-// pixel, the weight gradient contracts over the tile's 16 pixels, so both operands are
-// transposed through a per-wave LDS stage: the bf16 dz tile [16 px][64 ch] is written as the
-// lanes hold it and read back with ds_read_b64_tr_b16 as the A operand (row = channel, k =
-// pixel) of v_mfma_f32_16x16x16_bf16; the tile's 4 x 10 input halo patch (4 of the 8 padded
-// channels) is written from the conv's own fragments and read per lane as the B operand
-// (k = pixel, column = tap * 3 + c: 27 real columns in two 16-column tiles, the five spare
-// columns read the zero pad channel 3). 4 x 2 MFMAs per tile, 32 accumulator registers.
-// Measured (profiles/l0_wgrad_fused.md): 16.5 us + 6.2 us finish at b256 against 18.2 us dz
-// pass + 14.6 us WGRAD GEMM + 5.5 us finish; step 0.7017 vs 0.7389 ms, every trial of the A/B.
+// Layout: a wave owns 16 output pixels = 2 image rows x 8 columns = four whole 2x2 pool windows,
+// x 64 channels. The tile's pixels are numbered i = 4 * window + d, window 0..3 along the 8
+// columns and d = 2r + (c & 1) the position in the window (bn_act.hip order), so pixel i is tile
+// row (i >> 1) & 1, column 2 (i >> 2) + (i & 1). The conv is issued as mfma(x, weights): lane
+// (g = lane >> 4, rl = lane & 15) gathers tap 4t + g of pixel rl as the A operand and reads the
+// B operand from an LDS weight image staged once per block in permuted row order (row j * 16 + rl
+// holds channel 4 rl + j). The accumulator of column tile j then holds, in registers v = 0..3,
+// z of the four pixels of window g for channel 4 rl + j: a lane owns one pool window x four
+// consecutive channels. Everything after the conv follows from that:
+//   - the max, the first-maximum position, the ReLU cut and the winner's z of a window are over
+//     four registers of one lane: no cross-lane traffic, nothing computed twice, and all 64 lanes
+//     store (y and zw 8 B each, 128 B contiguous per window; the code one dword);
+//   - bias and the BatchNorm coefficients are 4 values per lane, held in registers;
+//   - the backward loads its window's dy (8 B) and code (one dword) once per lane;
+//   - the accumulator IS the A operand (row = channel slot rl, k = pixel 4g .. 4g+3) of the
+//     weight gradient's v_mfma_f32_16x16x16_bf16: dz goes from the epilogue's registers into
+//     the MFMA. Only the tile's 4 x 10 input halo patch (4 of the 8 padded channels) passes
+//     through LDS, written from the conv's own fragments and read per lane as the B operand
+//     (k = pixel, column = tap * 3 + c: 27 real columns in two 16-column tiles, the five spare
+//     columns read the zero pad channel 3). 4 x 2 MFMAs per tile, 32 accumulator registers; row
+//     4g + v of accumulator jt is channel 4 (4g + v) + jt.
+// The memory formats are independent of the lane layout: y, zw [N][H/2][W/2][64]; code bytes per
+// window in the order [g'][j'][v'] for channel j' * 16 + 4 g' + v' (read by l0_sums_kernel and
+// conv_igemm.hip BnBwdFuse::code), which for a lane's channels 4 rl + j is dword
+// (rl & 3) * 4 + (rl >> 2) of the window's 16, byte j.
+// The tile decode uses launch-constant FastDivs (common.h), the tap decode depends only on the
+// lane and is done once per kernel. Measured: profiles/l0_lane_layout.md (this layout against
+// the lane = pixel layout it replaces, profiles/l0_wgrad_fused.md).
 #include "common.h"
 #include "api.h"
 
@@ -67,6 +75,8 @@ struct Args {
   const unsigned short* wc;  // [64][3][3][8] bf16
   const float* bias;         // [64] or null
   int N, H, W, tiles;        // tiles = N * (H / 2) * (W / 8)
+  int wb, per_img;           // tiles per tile row (W / 8) and per image, and their FastDivs
+  FastDiv wb_d, per_img_d;
   float eps;
   int relu;
   float* stats;              // [kStatRep][2][64] forward sums (zeroed per step)
@@ -78,9 +88,9 @@ struct Args {
   float* sums;               // [kStatRep][2][64] BN-backward sums (zeroed per step)
   unsigned short* dz;        // [N][H][W][64] gradient at z
   unsigned* code;            // per pool window and channel: the position (0..3) that takes the
-                             // gradient, 4 = none (ReLU cut), 0xFF = NaN window; lane-major
-                             // [window][g][j][v] bytes, written by the forward, read by both
-                             // backward passes
+                             // gradient, 4 = none (ReLU cut), 0xFF = NaN window; bytes
+                             // [window][g'][j'][v'] for channel j'*16 + 4g' + v', written by the
+                             // forward, read by both backward passes
   unsigned short* zw;        // [N][H/2][W/2][64] bf16: z of the pixel code points to (forward;
                              // the backward sums need nothing else of the window)
   float* dgamma;             // accumulated (arena)
@@ -92,65 +102,98 @@ typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bf16x8 as_bf(const uint4& v) { return __builtin_bit_cast(bf16x8, v); }
 
-// lane l of each 16-lane row <- lane l ^ 1 / l ^ 8
-__device__ __forceinline__ float xor1(float v) { return dpp_f<0xB1>(v); }
-__device__ __forceinline__ float xor8(float v) { return dpp_f<0x128>(v); }  // row_ror:8
-
-struct Tile {
-  int n, h, w;  // this lane's pixel
-  int hp, wo;   // its pool window (pooled row / column)
-  int d;        // its position in the window (bn_act.hip order: 0 (0,0), 1 (0,1), 2 (1,0), 3 (1,1))
+// What depends on the lane alone, decoded once per kernel: the pixel the lane gathers for the
+// conv's A operand (pixel rl in window order) and, per k-step, its tap's offset from the tile's
+// corner. A tap past the 9 real ones gets a row far outside the image: its bounds check fails.
+struct Lane {
+  int g, rl;
+  int ph[kNKS], pw[kNKS];  // row / column of tap 4t + g of pixel rl, relative to the tile
 };
 
-__device__ __forceinline__ Tile tile_pixel(const Args& a, int t, int rl) {
-  const int wb = a.W / 8, per_img = (a.H / 2) * wb;
+__device__ __forceinline__ Lane lane_setup() {
+  Lane ln;
+  const int lane = threadIdx.x & 63;
+  ln.g = lane >> 4;
+  ln.rl = lane & 15;
+  const int pr = (ln.rl >> 1) & 1, pc = 2 * (ln.rl >> 2) + (ln.rl & 1);
+#pragma unroll
+  for (int t = 0; t < kNKS; ++t) {
+    const int tap = 4 * t + ln.g;
+    const int r = tap / 3, s = tap - r * 3;
+    ln.ph[t] = tap < 9 ? pr + r - 1 : -(1 << 20);
+    ln.pw[t] = pc + s - 1;
+  }
+  return ln;
+}
+
+// A tile (uniform over the wave): image, pooled row, block of 8 columns
+struct Tile {
+  int n, hp, cb;
+};
+
+__device__ __forceinline__ Tile tile_of(const Args& a, int t) {
   Tile p;
-  p.n = t / per_img;
-  const int rem = t - p.n * per_img;
-  p.hp = rem / wb;
-  const int cb = rem - p.hp * wb;
-  const int r = rl >> 3, c = rl & 7;
-  p.h = 2 * p.hp + r;
-  p.w = 8 * cb + c;
-  p.wo = 4 * cb + (c >> 1);
-  p.d = 2 * r + (c & 1);
+  p.n = fast_div(t, a.per_img_d);
+  const int rem = t - p.n * a.per_img;
+  p.hp = fast_div(rem, a.wb_d);
+  p.cb = rem - p.hp * a.wb;
   return p;
+}
+
+// the lane's pool window: window g of the tile
+__device__ __forceinline__ size_t window_of(const Args& a, const Tile& p, int g) {
+  return ((size_t)p.n * (a.H / 2) + p.hp) * (a.W / 2) + 4 * p.cb + g;
 }
 
 // LDS weight image [64 rows][13 taps][8 ch] (12 used taps + 1 pad tap per row spreads the 16
 // rows a ds_read_b128 lane group reads over the banks, conv_smallk.hip's stem layout), staged
-// once per block: the per-wave register copy of round-4's first version cost 48 VGPRs and
-// capped the kernel at 2 waves per SIMD
+// once per block: a per-wave register copy costs 48 VGPRs and caps the kernel at 2 waves per
+// SIMD. Row j * 16 + rl holds channel 4 rl + j (the lane layout above).
 constexpr int kRow = 13;
 struct Smem {
   uint4 w[kK * kRow];
-  float cf[7][kK];  // 0 scale, 1 shift, 2 mean, 3 inv-std, 4 / 5 backward sums, 6 bias
-  float red[4][2][kK];
+  float cf[3][kK];  // forward: 0 scale, 1 shift; backward: 0 scale, 1 / 2 the dz coefficients
 };
 
 __device__ __forceinline__ void stage_weights(const Args& a, Smem& sm) {
   for (int i = threadIdx.x; i < kK * 12; i += 256) {
-    const int k = i / 12, tap = i - k * 12;
-    sm.w[k * kRow + tap] = tap < 9 ? *reinterpret_cast<const uint4*>(a.wc + ((size_t)k * 9 + tap) * 8)
-                                   : make_uint4(0, 0, 0, 0);
+    const int row = i / 12, tap = i - row * 12;
+    const int k = 4 * (row & 15) + (row >> 4);
+    sm.w[row * kRow + tap] = tap < 9 ? *reinterpret_cast<const uint4*>(a.wc + ((size_t)k * 9 + tap) * 8)
+                                     : make_uint4(0, 0, 0, 0);
   }
 }
 
-// activation fragments of one tile: lane l loads tap 4t + (l >> 4) of its pixel (16 B)
-__device__ __forceinline__ void load_x(const Args& a, const Tile& p, int g, uint4 (&xf)[kNKS]) {
+// the lane's 4 values (channels 4 rl .. 4 rl + 3) of a per-channel table
+__device__ __forceinline__ void lane4(const float* tab, int rl, float (&v)[kNT]) {
+  const float4 q = *reinterpret_cast<const float4*>(tab + 4 * rl);
+  v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+
+__device__ __forceinline__ void lane_bias(const Args& a, int rl, float (&b)[kNT]) {
+#pragma unroll
+  for (int j = 0; j < kNT; ++j) b[j] = a.bias ? a.bias[4 * rl + j] : 0.f;
+}
+
+// activation fragments of one tile: the lane loads tap 4t + g of its gathered pixel (16 B)
+__device__ __forceinline__ void load_x(const Args& a, const Tile& p, const Lane& ln,
+                                       uint4 (&xf)[kNKS]) {
+  // (32-bit offsets: l0_shape_ok bounds N * H * W * 64 by 2^31)
+  const int corner = (p.n * a.H + 2 * p.hp) * a.W + 8 * p.cb;
 #pragma unroll
   for (int t = 0; t < kNKS; ++t) {
-    const int tap = 4 * t + g;
-    const int r = tap / 3, s = tap - r * 3;
-    const int h = p.h + r - 1, w = p.w + s - 1;
-    xf[t] = (tap < 9 && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W)
-                ? *reinterpret_cast<const uint4*>(a.x + (((size_t)p.n * a.H + h) * a.W + w) * 8)
+    const int h = 2 * p.hp + ln.ph[t], w = 8 * p.cb + ln.pw[t];
+    xf[t] = ((unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W)
+                ? *reinterpret_cast<const uint4*>(
+                      a.x + (unsigned)((corner + ln.ph[t] * a.W + ln.pw[t]) * 8))
                 : make_uint4(0, 0, 0, 0);
   }
 }
 
-// z of this lane's pixel for channels j*16 + 4g + v (bf16-rounded, + bias): conv_smallk.hip math
-__device__ __forceinline__ void conv_z(const Smem& sm, const uint4 (&xf)[kNKS], int g, int rl,
+// z[j][v] of the lane's window g: position v, channel 4 rl + j (bf16-rounded, + bias);
+// conv_smallk.hip math with the operands exchanged: A = pixels, B = channels
+__device__ __forceinline__ void conv_z(const Smem& sm, const uint4 (&xf)[kNKS],
+                                       const float (&bias)[kNT], int g, int rl,
                                        float (&z)[kNT][4]) {
   f32x4 acc[kNT];
 #pragma unroll
@@ -159,96 +202,83 @@ __device__ __forceinline__ void conv_z(const Smem& sm, const uint4 (&xf)[kNKS], 
   for (int t = 0; t < kNKS; ++t)
 #pragma unroll
     for (int j = 0; j < kNT; ++j)
-      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf(sm.w[(j * 16 + rl) * kRow + 4 * t + g]),
-                                                      as_bf(xf[t]), acc[j], 0, 0, 0);
+      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          as_bf(xf[t]), as_bf(sm.w[(j * 16 + rl) * kRow + 4 * t + g]), acc[j], 0, 0, 0);
 #pragma unroll
   for (int j = 0; j < kNT; ++j)
 #pragma unroll
-    for (int v = 0; v < 4; ++v) z[j][v] = bf2f(f2bf(acc[j][v] + sm.cf[6][j * 16 + 4 * g + v]));
+    for (int v = 0; v < 4; ++v) z[j][v] = bf2f(f2bf(acc[j][v] + bias[j]));
 }
 
-__device__ __forceinline__ void stage_bias(const Args& a, Smem& sm) {
-  if (threadIdx.x < kK) sm.cf[6][threadIdx.x] = a.bias ? a.bias[threadIdx.x] : 0.f;
-}
-
-__device__ __forceinline__ int xor1i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false); }
-__device__ __forceinline__ int xor8i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false); }
-
-// max over the pool window (lanes l, l^1, l^8, l^9), NaN-propagating like bn_act.hip's pool
-__device__ __forceinline__ float window_max(float v) {
-  v = __builtin_elementwise_maximum(v, xor1(v));
-  return __builtin_elementwise_maximum(v, xor8(v));
-}
-
-// block reduction of per-lane channel sums (lane: channels j*16 + 4g + v) -> one atomic per
-// channel per block into replica blockIdx.x % kStatRep (conv_smallk.hip scheme)
-__device__ __forceinline__ void block_sums(float (&s1)[kNT][4], float (&s2)[kNT][4], float* rep,
-                                           int rl, int g, Smem& sm) {
-#pragma unroll
-  for (int j = 0; j < kNT; ++j)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      s1[j][v] = dpp_sum16(s1[j][v]);
-      s2[j][v] = dpp_sum16(s2[j][v]);
-    }
-  const int wib = threadIdx.x >> 6;
-  if (rl == 0) {
-#pragma unroll
-    for (int j = 0; j < kNT; ++j)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        sm.red[wib][0][j * 16 + 4 * g + v] = s1[j][v];
-        sm.red[wib][1][j * 16 + 4 * g + v] = s2[j][v];
-      }
-  }
+// block reduction of per-lane channel sums (lane: channels 4 rl + j of its windows): the 16
+// (wave, g) partials of a channel are summed through LDS in the fixed order of their slots ->
+// one atomic per channel per block into replica blockIdx.x % kStatRep (conv_smallk.hip scheme)
+__device__ __forceinline__ void block_sums(const float (&s1)[kNT], const float (&s2)[kNT],
+                                           float* rep, int g, int rl, float (&red)[16][2][kK]) {
+  const int slot = (threadIdx.x >> 6) * 4 + g;
+  *reinterpret_cast<float4*>(&red[slot][0][4 * rl]) = make_float4(s1[0], s1[1], s1[2], s1[3]);
+  *reinterpret_cast<float4*>(&red[slot][1][4 * rl]) = make_float4(s2[0], s2[1], s2[2], s2[3]);
   __syncthreads();
   if (threadIdx.x < 2 * kK) {
     const int k = threadIdx.x / kK, c = threadIdx.x - k * kK;
-    atomicAdd(rep + k * kK + c,
-              stat_val(sm.red[0][k][c] + sm.red[1][k][c] + sm.red[2][k][c] + sm.red[3][k][c],
-                       blockIdx.x));
+    float t = red[0][k][c];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) t += red[i][k][c];
+    atomicAdd(rep + k * kK + c, stat_val(t, blockIdx.x));
   }
 }
 
-// one tile's global operands: the input fragments and (backward) the pooled gradient of the
-// lane's window (the four lanes of a window load the same 8 B)
+// one tile's global operands: the input fragments and (backward) the pooled gradient and the
+// forward's verdicts of the lane's window x 4 channels
 struct Ops {
   uint4 x[kNKS];
-  u16x4 dy[kNT];
-  uint4 code;
+  u16x4 dy;
+  unsigned code;
 };
 
-__device__ __forceinline__ size_t window_of(const Args& a, const Tile& p) {
-  return ((size_t)p.n * (a.H / 2) + p.hp) * (a.W / 2) + p.wo;
-}
+// the lane's code dword within its window's 16 (the byte order of Args::code)
+__device__ __forceinline__ int code_dword(int rl) { return (rl & 3) * 4 + (rl >> 2); }
 
 template <bool DY>
-__device__ __forceinline__ void load_ops(const Args& a, const Tile& p, int g, Ops& o) {
-  load_x(a, p, g, o.x);
+__device__ __forceinline__ void load_ops(const Args& a, const Tile& p, const Lane& ln, Ops& o) {
+  load_x(a, p, ln, o.x);
   if (DY) {
-    const size_t win = window_of(a, p);
-    const unsigned short* src = a.dy + win * kK + 4 * g;
-#pragma unroll
-    for (int j = 0; j < kNT; ++j) o.dy[j] = *reinterpret_cast<const u16x4*>(src + j * 16);
-    o.code = *reinterpret_cast<const uint4*>(a.code + win * (kK / 4) + g * 4);
+    const size_t win = window_of(a, p, ln.g);
+    o.dy = *reinterpret_cast<const u16x4*>(a.dy + win * kK + 4 * ln.rl);
+    o.code = a.code[win * (kK / 4) + code_dword(ln.rl)];
   }
 }
 
 // Work split: a block = 4 waves, a wave walks tiles wave, wave + nw, ... (at most 1024 blocks:
 // every block ends with one atomic per channel into a statistics replica). Latency is hidden by
-// occupancy (waves per SIMD): prefetching the next tile's operands into registers measured
-// slower (r4i: bwd 31 vs 28 us at b256, 176 VGPRs -> 2 waves per SIMD).
-template <bool DY, class Setup, class Body>
-__device__ __forceinline__ void tile_loop(const Args& a, int g, int rl, Setup setup, Body body) {
+// occupancy (waves per SIMD). Called after the block's setup and its barrier.
+// PF: the next tile's operands are loaded into registers before this tile's body. Measured per
+// kernel (profiles/l0_lane_layout.md): the statistics pass gains (9.3-9.5 vs 9.8-10.1 us at
+// b256, 4.7 vs 5.4 us at b32), the forward loses (13.7-14.0 vs 13.1-13.2 us), and the fused
+// backward does not fit it into its 128 registers (76 B of scratch), so only l0_stats takes it.
+template <bool DY, bool PF, class Body>
+__device__ __forceinline__ void tile_loop(const Args& a, const Lane& ln, Body body) {
   const int nw = gridDim.x * 4;
-  setup();
-  __syncthreads();
-  for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < a.tiles; t += nw) {
+  int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (PF) {
+    if (t >= a.tiles) return;
+    Ops nxt;
+    load_ops<DY>(a, tile_of(a, t), ln, nxt);
+    for (; t < a.tiles; t += nw) {
+      asm volatile("" ::: "memory");
+      const Tile cur = tile_of(a, t);
+      const Ops op = nxt;
+      if (t + nw < a.tiles) load_ops<DY>(a, tile_of(a, t + nw), ln, nxt);
+      body(cur, op);
+    }
+    return;
+  }
+  for (; t < a.tiles; t += nw) {
     // keeps the LDS weight reads inside the loop (hoisted, they are 48 VGPRs)
     asm volatile("" ::: "memory");
-    const Tile cur = tile_pixel(a, t, rl);
+    const Tile cur = tile_of(a, t);
     Ops op;
-    load_ops<DY>(a, cur, g, op);
+    load_ops<DY>(a, cur, ln, op);
     body(cur, op);
   }
 }
@@ -256,103 +286,93 @@ __device__ __forceinline__ void tile_loop(const Args& a, int g, int rl, Setup se
 // forward statistics of z (no store)
 __global__ __launch_bounds__(256) void l0_stats_kernel(Args a) {
   __shared__ Smem sm;
-  const int lane = threadIdx.x & 63, g = lane >> 4, rl = lane & 15;
-  float s1[kNT][4] = {}, s2[kNT][4] = {};
-  tile_loop<false>(
-      a, g, rl,
-      [&] {
-        stage_weights(a, sm);
-        stage_bias(a, sm);
-      },
-      [&](const Tile&, const Ops& op) {
-        float z[kNT][4];
-        conv_z(sm, op.x, g, rl, z);
+  __shared__ float red[16][2][kK];
+  const Lane ln = lane_setup();
+  float bias[kNT], s1[kNT] = {}, s2[kNT] = {};
+  stage_weights(a, sm);
+  lane_bias(a, ln.rl, bias);
+  __syncthreads();
+  tile_loop<false, true>(a, ln, [&](const Tile&, const Ops& op) {
+    float z[kNT][4];
+    conv_z(sm, op.x, bias, ln.g, ln.rl, z);
 #pragma unroll
-        for (int j = 0; j < kNT; ++j)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            s1[j][v] += z[j][v];
-            s2[j][v] += z[j][v] * z[j][v];
-          }
-      });
-  block_sums(s1, s2, a.stats + stat_rep(blockIdx.x) * 2 * kK, rl, g, sm);
+    for (int j = 0; j < kNT; ++j) {
+      s1[j] += (z[j][0] + z[j][1]) + (z[j][2] + z[j][3]);
+      s2[j] += (z[j][0] * z[j][0] + z[j][1] * z[j][1]) + (z[j][2] * z[j][2] + z[j][3] * z[j][3]);
+    }
+  });
+  block_sums(s1, s2, a.stats + stat_rep(blockIdx.x) * 2 * kK, ln.g, ln.rl, red);
 }
 
 __global__ __launch_bounds__(256) void l0_fwd_kernel(Args a) {
   __shared__ Smem sm;
-  const int lane = threadIdx.x & 63, g = lane >> 4, rl = lane & 15;
-  const int Ho = a.H / 2, Wo = a.W / 2;
-  tile_loop<false>(
-      a, g, rl,
-      [&] {
-        stage_weights(a, sm);
-        stage_bias(a, sm);
-        if (threadIdx.x < kK) {  // (scale, shift) from the statistics replicas (bn_act.hip finalize)
-          const int c = threadIdx.x;
-          const float M = (float)a.N * a.H * a.W;
-          float s1 = 0.f, s2 = 0.f;
+  const Lane ln = lane_setup();
+  stage_weights(a, sm);
+  if (threadIdx.x < kK) {  // (scale, shift) from the statistics replicas (bn_act.hip finalize)
+    const int c = threadIdx.x;
+    const float M = (float)a.N * a.H * a.W;
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-          for (int r = 0; r < kStatRep; ++r) {
-            s1 += a.stats[r * 2 * kK + c];
-            s2 += a.stats[r * 2 * kK + kK + c];
-          }
-          const float mu = s1 / M;
-          const float var = fmaxf(s2 / M - mu * mu, 0.f);
-          const float is = rsqrtf(var + a.eps);
-          const float sc = a.gamma[c] * is, sh = a.beta[c] - mu * sc;
-          sm.cf[0][c] = sc;
-          sm.cf[1][c] = sh;
-          if (blockIdx.x == 0) {  // the table the backward reads
-            a.coef[0 * kK + c] = sc;
-            a.coef[1 * kK + c] = sh;
-            a.coef[2 * kK + c] = mu;
-            a.coef[3 * kK + c] = is;
-          }
-        }
-      },
-      [&](const Tile& cur, const Ops& op) {
-        float z[kNT][4];
-        conv_z(sm, op.x, g, rl, z);
-        const int bit = 1 << cur.d, upto = (2 << cur.d) - 1;
-        u16x4 o[kNT], ow[kNT];
-        unsigned cw[kNT];
+    for (int r = 0; r < kStatRep; ++r) {
+      s1 += a.stats[r * 2 * kK + c];
+      s2 += a.stats[r * 2 * kK + kK + c];
+    }
+    const float mu = s1 / M;
+    const float var = fmaxf(s2 / M - mu * mu, 0.f);
+    const float is = rsqrtf(var + a.eps);
+    const float sc = a.gamma[c] * is, sh = a.beta[c] - mu * sc;
+    sm.cf[0][c] = sc;
+    sm.cf[1][c] = sh;
+    if (blockIdx.x == 0) {  // the table the backward reads
+      a.coef[0 * kK + c] = sc;
+      a.coef[1 * kK + c] = sh;
+      a.coef[2 * kK + c] = mu;
+      a.coef[3 * kK + c] = is;
+    }
+  }
+  float bias[kNT], sc[kNT], sh[kNT];
+  lane_bias(a, ln.rl, bias);
+  __syncthreads();
+  lane4(sm.cf[0], ln.rl, sc);
+  lane4(sm.cf[1], ln.rl, sh);
+  tile_loop<false, false>(a, ln, [&](const Tile& cur, const Ops& op) {
+    float z[kNT][4];
+    conv_z(sm, op.x, bias, ln.g, ln.rl, z);
+    u16x4 o, ow;
+    unsigned cw = 0;
 #pragma unroll
-        for (int j = 0; j < kNT; ++j) {
-          cw[j] = 0;
+    for (int j = 0; j < kNT; ++j) {
+      float y[4];
 #pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int c = j * 16 + 4 * g + v;
-            float y = z[j][v] * sm.cf[0][c] + sm.cf[1][c];  // (bn_act.hip apply expression)
-            if (a.relu) y = fmaxf(y, 0.f);
-            const float m = window_max(y);
-            o[j][v] = f2bf(m);
-            // the gradient's destination: the window's first maximum (bn_act.hip's tie rule:
-            // every lane sets bit d when it holds the max, the lowest bit of the OR wins),
-            // none when ReLU zeroed the whole window (its winner had y <= 0)
-            int b = y == m ? bit : 0;
-            b |= xor1i(b);
-            b |= xor8i(b);
-            const unsigned cd = b == 0 ? 0xFFu : (a.relu && !(m > 0.f)) ? 4u : (unsigned)__builtin_ctz(b);
-            cw[j] |= cd << (8 * v);
-            // the winner's z to every lane of the window (the others add exact zeros)
-            float zs = (b & upto) == bit ? z[j][v] : 0.f;
-            zs += xor1(zs);
-            zs += xor8(zs);
-            ow[j][v] = f2bf(zs);  // (exact: z is bf16-valued)
-          }
-        }
-        if (cur.d == 0) {
-          const size_t win = window_of(a, cur);
-          unsigned short* dst = a.y + win * kK + 4 * g;
+      for (int v = 0; v < 4; ++v) {
+        y[v] = z[j][v] * sc[j] + sh[j];  // (bn_act.hip apply expression)
+        // NaN-propagating like the pool's max: a NaN in the statistics marks every window
+        if (a.relu) y[v] = __builtin_elementwise_maximum(y[v], 0.f);
+      }
+      // max over the window, NaN-propagating like bn_act.hip's pool
+      const float m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(y[0], y[1]),
+                                                    __builtin_elementwise_maximum(y[2], y[3]));
+      // the gradient's destination: the window's first maximum in window order (bn_act.hip's
+      // tie rule), 0xFF when no value equals the max (a NaN window), 4 = none when ReLU zeroed
+      // the whole window (its winner had y <= 0); zw is the first maximum's z either way
+      unsigned pos = 0xFFu;
+      float zs = 0.f;
 #pragma unroll
-          for (int j = 0; j < kNT; ++j) *reinterpret_cast<u16x4*>(dst + j * 16) = o[j];
-          unsigned short* dzw = a.zw + win * kK + 4 * g;
-#pragma unroll
-          for (int j = 0; j < kNT; ++j) *reinterpret_cast<u16x4*>(dzw + j * 16) = ow[j];
-          *reinterpret_cast<uint4*>(a.code + win * (kK / 4) + g * 4) =
-              make_uint4(cw[0], cw[1], cw[2], cw[3]);
-        }
-      });
+      for (int v = 3; v >= 0; --v) {
+        const bool hit = y[v] == m;
+        pos = hit ? (unsigned)v : pos;
+        zs = hit ? z[j][v] : zs;
+      }
+      const unsigned cd = pos == 0xFFu ? 0xFFu : (a.relu && !(m > 0.f)) ? 4u : pos;
+      cw |= cd << (8 * j);
+      o[j] = f2bf(m);
+      ow[j] = f2bf(zs);  // (exact: z is bf16-valued)
+    }
+    const size_t win = window_of(a, cur, ln.g);
+    *reinterpret_cast<u16x4*>(a.y + win * kK + 4 * ln.rl) = o;
+    *reinterpret_cast<u16x4*>(a.zw + win * kK + 4 * ln.rl) = ow;
+    a.code[win * (kK / 4) + code_dword(ln.rl)] = cw;
+  });
 }
 
 // BatchNorm-backward sums S1 = sum dy_bn, S2 = sum dy_bn * xhat without the conv: dy_bn is the
@@ -410,34 +430,33 @@ __global__ __launch_bounds__(256) void l0_sums_kernel(Args a, int windows) {
 
 // ---- weight gradient fused into the dz pass (APPLY = 2)
 typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
 constexpr int kWgN = 28;            // partial's columns: n = tap * 3 + c < 27, + 1 (16-B rows)
 constexpr int kWgSlab = kK * kWgN;  // fp32 per block partial (7 KB)
-// dz tile row: 64 channels + 4 pad = 34 dwords, so the 16 lanes of a ds_write_b64 group (one
-// pixel row each) land on 16 distinct bank pairs
-constexpr int kDzRow = 68;
 struct alignas(16) WgStage {        // per wave
-  unsigned short dz[16][kDzRow];    // this tile's bf16 dz [pixel][channel]
-  unsigned short xp[4 * 10][4];     // its input halo patch [row][column][channels 0..3]
+  unsigned short xp[4 * 10][4];     // this tile's input halo patch [row][column][channels 0..3]
 };
 template <bool ON> struct WgLds { WgStage w[4]; };
 template <> struct WgLds<false> {};
 
-// BN backward through the recomputed z. APPLY = 0: S1 / S2 sums; 1: dz (+ dgamma / dbeta);
-// 2: dz kept on chip and contracted with the input patch into the weight gradient partial
+// BN backward through the recomputed z. APPLY = 1: dz stored (+ dgamma / dbeta); 2: dz kept in
+// registers and contracted with the input patch into the weight gradient partial
 template <int APPLY>
 __device__ __forceinline__ void l0_bwd_body(const Args& a) {
+  static_assert(APPLY == 1 || APPLY == 2, "dz is stored or chained into the weight gradient");
   constexpr bool WG = APPLY == 2;
   __shared__ Smem sm;
   __shared__ WgLds<WG> wl;
-  const int lane = threadIdx.x & 63, g = lane >> 4, rl = lane & 15, wib = threadIdx.x >> 6;
-  float s1[kNT][4] = {}, s2[kNT][4] = {};
-  // WG: dW[channel jt*16 + 4g + v][column nt*16 + rl] of this wave's tiles
+  const Lane ln = lane_setup();
+  const int g = ln.g, rl = ln.rl, wib = threadIdx.x >> 6;
+  // WG: dW[channel 4 (4g + v) + jt][column nt*16 + rl] of this wave's tiles
   f32x4 dwacc[kNT][2];
-  // ... and this lane's B-operand source in the patch: column n = nt*16 + rl = tap * 3 + c at
-  // the tile pixels 4g .. 4g+3 (tile row g >> 1, columns 4 (g & 1) + j; + 4 u16 per pixel);
-  // n >= 27 reads the zero pad channel 3
+  // ... this lane's B-operand source in the patch: column n = nt*16 + rl = tap * 3 + c at the
+  // tile pixels 4g .. 4g+3 = window g, positions 0..3 (+0, +1, +10, +11 patch pixels of 4 u16
+  // from the window's corner, tile column 2g); n >= 27 reads the zero pad channel 3
   int xoff[2] = {0, 0};
+  // ... and where its conv fragments go in the patch: tap (tr, ts) of tile pixel (r, c) is patch
+  // position (r + tr, c + ts); -1 = no tap
+  int pidx[kNKS] = {0, 0, 0};
   if (WG) {
 #pragma unroll
     for (int jt = 0; jt < kNT; ++jt)
@@ -448,112 +467,105 @@ __device__ __forceinline__ void l0_bwd_body(const Args& a) {
       const int n = nt * 16 + rl;
       const int tap = n < 27 ? n / 3 : 0, c = n < 27 ? n - tap * 3 : 3;
       const int tr = tap / 3, ts = tap - tr * 3;
-      xoff[nt] = (((g >> 1) + tr) * 10 + 4 * (g & 1) + ts) * 4 + c;
+      xoff[nt] = ((tr * 10) + 2 * g + ts) * 4 + c;
+    }
+#pragma unroll
+    for (int t = 0; t < kNKS; ++t)
+      pidx[t] = 4 * t + g < 9 ? (ln.ph[t] + 1) * 10 + ln.pw[t] + 1 : -1;
+  }
+  stage_weights(a, sm);
+  if (threadIdx.x < kK) {
+    const int c = threadIdx.x;
+    // LDS rows: 0 scale, 1 / 2 with dz = scale * dy_bn + z * [1] + [2], the bn_act.hip apply
+    // expression scale * (dy_bn - k1 - xhat * k2) expanded in z; k1 / k2 from the finalize of
+    // the backward sums (bn_act.hip bn_finalize_bwd_kernel)
+    const float sc = a.coef[c], mu = a.coef[2 * kK + c], is = a.coef[3 * kK + c];
+    const float inv_m = 1.f / ((float)a.N * a.H * a.W);
+    float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < kStatRep; ++r) {
+      t1 += a.sums[r * 2 * kK + c];
+      t2 += a.sums[r * 2 * kK + kK + c];
+    }
+    const float k1 = t1 * inv_m, k2 = t2 * inv_m;
+    sm.cf[0][c] = sc;
+    sm.cf[1][c] = -sc * k2 * is;
+    sm.cf[2][c] = sc * (k2 * is * mu - k1);
+    if (blockIdx.x == 0) {
+      a.coef[4 * kK + c] = k1;
+      a.coef[5 * kK + c] = k2;
+      if (a.dgamma) a.dgamma[c] += t2;  // one writer per channel
+      if (a.dbeta) a.dbeta[c] += t1;
     }
   }
-  tile_loop<true>(
-      a, g, rl,
-      [&] {
-        stage_weights(a, sm);
-        stage_bias(a, sm);
-        if (threadIdx.x < kK) {
-          const int c = threadIdx.x;
-          // LDS rows: 0 scale, 2 invstd, 3 -mean * invstd (xhat = z * [2] + [3]); APPLY:
-          // 4 / 5 with dz = scale * dy_bn + z * [4] + [5], the bn_act.hip apply expression
-          // scale * (dy_bn - k1 - xhat * k2) expanded in z
-          const float sc = a.coef[c], mu = a.coef[2 * kK + c], is = a.coef[3 * kK + c];
-          sm.cf[0][c] = sc;
-          sm.cf[2][c] = is;
-          sm.cf[3][c] = -mu * is;
-          if (APPLY) {  // finalize of the backward sums (bn_act.hip bn_finalize_bwd_kernel)
-            const float inv_m = 1.f / ((float)a.N * a.H * a.W);
-            float t1 = 0.f, t2 = 0.f;
+  float bias[kNT], sc[kNT], cz[kNT], c0[kNT];
+  lane_bias(a, rl, bias);
+  __syncthreads();
+  lane4(sm.cf[0], rl, sc);
+  lane4(sm.cf[1], rl, cz);
+  lane4(sm.cf[2], rl, c0);
+  tile_loop<true, false>(a, ln, [&](const Tile& cur, const Ops& op) {
+    if constexpr (WG) {
+      // the halo patch from the conv's fragments; positions shared by several lanes get the
+      // same value
+      WgStage& st = wl.w[wib];
 #pragma unroll
-            for (int r = 0; r < kStatRep; ++r) {
-              t1 += a.sums[r * 2 * kK + c];
-              t2 += a.sums[r * 2 * kK + kK + c];
-            }
-            const float k1 = t1 * inv_m, k2 = t2 * inv_m;
-            sm.cf[4][c] = -sc * k2 * is;
-            sm.cf[5][c] = sc * (k2 * is * mu - k1);
-            if (blockIdx.x == 0) {
-              a.coef[4 * kK + c] = k1;
-              a.coef[5 * kK + c] = k2;
-              if (a.dgamma) a.dgamma[c] += t2;  // one writer per channel
-              if (a.dbeta) a.dbeta[c] += t1;
-            }
-          }
-        }
-      },
-      [&](const Tile& cur, const Ops& op) {
-        if constexpr (WG) {
-          // the halo patch from the conv's fragments: tap (tr, ts) of pixel (r, c) is patch
-          // position (r + tr, c + ts); positions shared by several lanes get the same value
-          WgStage& st = wl.w[wib];
+      for (int t = 0; t < kNKS; ++t)
+        if (pidx[t] >= 0)
+          *reinterpret_cast<uint2*>(st.xp[pidx[t]]) = make_uint2(op.x[t].x, op.x[t].y);
+    }
+    float z[kNT][4];
+    conv_z(sm, op.x, bias, g, rl, z);
+    u16x4 o[kNT];  // o[j][v]: dz of channel 4 rl + j at window position v
 #pragma unroll
-          for (int t = 0; t < kNKS; ++t) {
-            const int tap = 4 * t + g;
-            const int tr = tap / 3, ts = tap - tr * 3;
-            if (tap < 9)
-              *reinterpret_cast<uint2*>(st.xp[((rl >> 3) + tr) * 10 + (rl & 7) + ts]) =
-                  make_uint2(op.x[t].x, op.x[t].y);
-          }
-        }
-        float z[kNT][4];
-        conv_z(sm, op.x, g, rl, z);
-        const unsigned cw[kNT] = {op.code.x, op.code.y, op.code.z, op.code.w};
-        u16x4 o[kNT];
+    for (int j = 0; j < kNT; ++j) {
+      const unsigned cd = (op.code >> (8 * j)) & 0xFFu;
+      const float dyv = bf2f(op.dy[j]);
 #pragma unroll
-        for (int j = 0; j < kNT; ++j)
+      for (int v = 0; v < 4; ++v) {
+        // the forward's verdict: this position takes the pooled gradient
+        const float dyb = cd == (unsigned)v ? dyv : 0.f;
+        o[j][v] = f2bf(sc[j] * dyb + (z[j][v] * cz[j] + c0[j]));
+      }
+    }
+    if constexpr (WG) {
+      // dW += dz^T x over the tile's 16 pixels: o[jt] is the A operand as it stands (row rl =
+      // channel 4 rl + jt, k = pixels 4g .. 4g+3). LDS accesses of one wave complete in program
+      // order, so the wave's own patch needs no barrier, only the compiler's order
+      asm volatile("" ::: "memory");
+      const unsigned short* xp = &wl.w[wib].xp[0][0];
+      v4i16 fb[2];
 #pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int c = j * 16 + 4 * g + v;
-            const float zf = z[j][v];
-            // the forward's verdict: this lane's pixel takes the pooled gradient
-            const float dyb = ((cw[j] >> (8 * v)) & 0xFFu) == (unsigned)cur.d ? bf2f(op.dy[j][v]) : 0.f;
-            if (APPLY) {
-              o[j][v] = f2bf(sm.cf[0][c] * dyb + (zf * sm.cf[4][c] + sm.cf[5][c]));
-            } else {
-              s1[j][v] += dyb;
-              s2[j][v] += dyb * (zf * sm.cf[2][c] + sm.cf[3][c]);
-            }
-          }
-        if constexpr (WG) {
-          // dW += dz^T x over the tile's 16 pixels. LDS accesses of one wave complete in
-          // program order, so the wave's own stage needs no barrier, only the compiler's order
-          WgStage& st = wl.w[wib];
+      for (int nt = 0; nt < 2; ++nt) {
+        fb[nt][0] = (short)xp[xoff[nt]];
+        fb[nt][1] = (short)xp[xoff[nt] + 4];
+        fb[nt][2] = (short)xp[xoff[nt] + 40];
+        fb[nt][3] = (short)xp[xoff[nt] + 44];
+      }
 #pragma unroll
-          for (int j = 0; j < kNT; ++j)
-            *reinterpret_cast<u16x4*>(&st.dz[rl][j * 16 + 4 * g]) = o[j];
-          asm volatile("" ::: "memory");
-          const unsigned short* xp = &st.xp[0][0];
-          v4i16 fb[2];
+      for (int jt = 0; jt < kNT; ++jt) {
+        const v4i16 fa = __builtin_bit_cast(v4i16, o[jt]);
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt)
+        for (int nt = 0; nt < 2; ++nt)
+          dwacc[jt][nt] =
+              __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(fa, fb[nt], dwacc[jt][nt], 0, 0, 0);
+      }
+    } else {
+      // pixel 4g + v: tile row v >> 1, column 2g + (v & 1); 128 B contiguous per 16 lanes
+      unsigned short* dst =
+          a.dz + (((size_t)cur.n * a.H + 2 * cur.hp) * a.W + 8 * cur.cb + 2 * g) * kK + 4 * rl;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) fb[nt][j] = (short)xp[xoff[nt] + 4 * j];
-          // A operand: lane group g reads pixels 4g .. 4g+3 x channels jt*16 .. +15 transposed
-          // (lane 4q + p supplies row q, columns 4p .. 4p+3; lane i receives column i)
-          const unsigned short* arow = &st.dz[4 * g + (rl >> 2)][4 * (rl & 3)];
-#pragma unroll
-          for (int jt = 0; jt < kNT; ++jt) {
-            const v4i16 fa = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(arow + jt * 16));
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-              dwacc[jt][nt] =
-                  __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(fa, fb[nt], dwacc[jt][nt], 0, 0, 0);
-          }
-        } else if (APPLY) {
-          unsigned short* dst = a.dz + (((size_t)cur.n * a.H + cur.h) * a.W + cur.w) * kK + 4 * g;
-#pragma unroll
-          for (int j = 0; j < kNT; ++j) *reinterpret_cast<u16x4*>(dst + j * 16) = o[j];
-        }
-      });
-  if (!APPLY) block_sums(s1, s2, a.sums + stat_rep(blockIdx.x) * 2 * kK, rl, g, sm);
+      for (int v = 0; v < 4; ++v) {
+        const u16x4 q = {o[0][v], o[1][v], o[2][v], o[3][v]};
+        *reinterpret_cast<u16x4*>(dst + ((size_t)(v >> 1) * a.W + (v & 1)) * kK) = q;
+      }
+    }
+  });
   if constexpr (WG) {
     // the block's partial: waves summed in the fixed order ((w0 + w1) + w2) + w3 through LDS
     // (the weight image's space, free after the tile loop), stored by wave 3 as [64][kWgN]
     float* red = reinterpret_cast<float*>(sm.w);
+    const int lane = threadIdx.x & 63;
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -570,7 +582,7 @@ __device__ __forceinline__ void l0_bwd_body(const Args& a) {
               if (w < 3) {
                 red[e * 64 + lane] = t;
               } else if (nt * 16 + rl < kWgN) {
-                a.wg[(size_t)blockIdx.x * kWgSlab + (jt * 16 + 4 * g + v) * kWgN + nt * 16 + rl] = t;
+                a.wg[(size_t)blockIdx.x * kWgSlab + (4 * (4 * g + v) + jt) * kWgN + nt * 16 + rl] = t;
               }
             }
       }
@@ -675,6 +687,10 @@ static l0::Args l0_args(const ConvGeom* g, const L0Io* io) {
   a.bias = io->bias;
   a.N = g->N; a.H = g->H; a.W = g->W;
   a.tiles = g->N * (g->H / 2) * (g->W / 8);
+  a.wb = g->W / 8;
+  a.per_img = (g->H / 2) * a.wb;
+  a.wb_d = make_fastdiv(a.wb);
+  a.per_img_d = make_fastdiv(a.per_img);
   a.eps = io->eps;
   a.relu = io->relu;
   a.stats = io->stats;
