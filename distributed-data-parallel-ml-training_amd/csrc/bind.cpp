@@ -606,6 +606,7 @@ PYBIND11_MODULE(_native, m) {
     ddp_sgd_tile_dims(RS, &tk, &tc);
     return std::make_pair(tk, tc);
   });
+  m.def("sgd_tile_limit", []() { return ddp_sgd_tile_limit(); });
   // sched (api.h LrSched) with sched_mode 1: whole advance, 2: the staged step becomes current
   m.def("counter_add", [](uintptr_t c, int delta, uintptr_t st, uintptr_t sched, int sched_mode) {
     check(ddp_counter_add(P<int>(c), delta, P<ddp_amd::LrSched>(sched), sched_mode, S(st)),

@@ -379,6 +379,7 @@ int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,
                    const ddp_amd::PackDesc* pack, int n_pack, unsigned* done, unsigned* signal,
                    const unsigned* skip, hipStream_t st);
 void ddp_sgd_tile_dims(int RS, int* TK, int* TC);
+int ddp_sgd_tile_limit();  // floats of the LDS tile: a tile item needs TK * TC * R * S <= this
 // c += delta (c may be null); with ``sched``, mode 1: a whole advance (step = next = step + 1,
 // the step's only launch), mode 2: the staged step becomes current (step = next)
 int ddp_counter_add(int* c, int delta, ddp_amd::LrSched* sched, int sched_mode, hipStream_t st);

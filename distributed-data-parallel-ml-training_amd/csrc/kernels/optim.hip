@@ -629,6 +629,10 @@ extern "C" void ddp_sgd_tile_dims(int RS, int* TK, int* TC) {
   else { *TK = 8; *TC = 16; }
 }
 
+// Floats of the tile kernel's LDS tile: a tile item needs TK * TC * R * S of them, and the
+// Python table builder refuses a tensor that needs more.
+extern "C" int ddp_sgd_tile_limit() { return kTileElems; }
+
 extern "C" int ddp_counter_add(int* c, int delta, LrSched* sched, int sched_mode,
                                hipStream_t st) {
   hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, st, c, delta, sched, sched_mode);

@@ -223,6 +223,12 @@ class FusedSGD(torch.optim.SGD):
                         per_param[i].append([2, s0, min(8192, n - s0), d])
                     continue
                 TK, TC = native().sgd_tile_dims(R * S)
+                if TK * TC * R * S > native().sgd_tile_limit():
+                    self._table_key = None  # (nothing was built: the next call refuses again)
+                    raise ValueError(
+                        f"parameter {i} (conv weight {K}x{Cr}x{R}x{S}, operand channels {C}): a "
+                        f"{TK} x {TC} tile of a {R}x{S} filter needs {TK * TC * R * S} floats, "
+                        f"the re-pack kernel's tile holds {native().sgd_tile_limit()}")
                 for k0 in range(0, K, TK):
                     for c0 in range(0, C, TC):
                         per_param[i].append([1, d, k0, c0])
