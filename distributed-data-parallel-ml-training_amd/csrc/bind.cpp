@@ -554,14 +554,17 @@ PYBIND11_MODULE(_native, m) {
                        uintptr_t skip, uintptr_t shadow, uintptr_t slot, uintptr_t done,
                        uintptr_t signal, uintptr_t sched, int sched_advance, uintptr_t lars_side,
                        uintptr_t lars_tensors, uintptr_t lars_partial, uintptr_t lars_trust,
-                       float lars_eta, float lars_eps) {
+                       float lars_eta, float lars_eps, uintptr_t clip_partial, int clip_chunks,
+                       float clip_max_norm, float clip_eps, int clip_flags,
+                       uintptr_t clip_stats) {
     check(ddp_sgd_pack(P<void>(items), n_items, P<long long>(descs), P<float>(p), P<float>(g),
                        P<float>(buf), lr, momentum, wd, grad_scale, nesterov, zero_grad,
                        P<int>(counter), delta, P<const unsigned>(skip), P<unsigned short>(shadow),
                        P<float>(slot), P<unsigned>(done), P<unsigned>(signal),
                        P<ddp_amd::LrSched>(sched), sched_advance, P<void>(lars_side),
                        P<void>(lars_tensors), P<void>(lars_partial), P<float>(lars_trust),
-                       lars_eta, lars_eps, S(st)),
+                       lars_eta, lars_eps, P<const float>(clip_partial), clip_chunks,
+                       clip_max_norm, clip_eps, clip_flags, P<float>(clip_stats), S(st)),
           "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
@@ -570,7 +573,17 @@ PYBIND11_MODULE(_native, m) {
      py::arg("done") = 0, py::arg("signal") = 0, py::arg("sched") = 0,
      py::arg("sched_advance") = 0, py::arg("lars_side") = 0, py::arg("lars_tensors") = 0,
      py::arg("lars_partial") = 0, py::arg("lars_trust") = 0, py::arg("lars_eta") = 0.f,
-     py::arg("lars_eps") = 0.f);
+     py::arg("lars_eps") = 0.f, py::arg("clip_partial") = 0, py::arg("clip_chunks") = 0,
+     py::arg("clip_max_norm") = 0.f, py::arg("clip_eps") = 0.f, py::arg("clip_flags") = 0,
+     py::arg("clip_stats") = 0);
+  // gradient guard (optim.hip grad_sumsq_kernel): per-chunk sum (g * grad_scale)^2 of every
+  // parameter chunk in the items, the input of sgd_pack's clip_* arguments
+  m.def("grad_sumsq", [](uintptr_t items, int n_items, uintptr_t g, float grad_scale,
+                         uintptr_t partial, uintptr_t st) {
+    check(ddp_grad_sumsq(P<void>(items), n_items, P<float>(g), grad_scale, P<float>(partial),
+                         S(st)), "grad_sumsq");
+  }, py::arg("items"), py::arg("n_items"), py::arg("grad"), py::arg("grad_scale"),
+     py::arg("partial"), py::arg("stream"));
   // LARS norms launch (optim.hip lars_norms_kernel): per-chunk {sum p^2, sum (g * grad_scale)^2}
   m.def("lars_norms", [](uintptr_t items, int n_items, uintptr_t p, uintptr_t g, float grad_scale,
                          uintptr_t partial, uintptr_t st) {

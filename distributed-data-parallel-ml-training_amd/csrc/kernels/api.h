@@ -365,7 +365,18 @@ int ddp_sgd_pack(const void* items, int n_items, const long long* descs, float* 
                  unsigned short* shadow, float* slot, unsigned* done, unsigned* signal,
                  ddp_amd::LrSched* sched, int sched_advance, const void* lars_side,
                  const void* lars_tensors, const void* lars_partial, float* lars_trust,
-                 float lars_eta, float lars_eps, hipStream_t st);
+                 float lars_eta, float lars_eps, const float* clip_partial, int clip_chunks,
+                 float clip_max_norm, float clip_eps, int clip_flags, float* clip_stats,
+                 hipStream_t st);
+// Gradient guard (optim.hip ClipArgs, optim/sgd.py max_grad_norm / skip_nonfinite):
+// ``clip_partial`` non-null selects the clipped instantiation of ddp_sgd_pack (plain or LARS) —
+// one float per 8192-element chunk of the WHOLE arena (``clip_chunks`` of them), sum
+// (g * grad_scale)^2 as written by ddp_grad_sumsq, launched before it (int4 items {arena offset,
+// count <= 8192, global chunk, -}, one block each); ``clip_flags``: 1 = clip to
+// ``clip_max_norm``, 2 = skip a step whose norm is not finite, 4 = this launch ends the step (a
+// skipped step is counted); ``clip_stats``: 4 words {norm, coefficient, skipped steps (u32), -}
+int ddp_grad_sumsq(const void* items, int n_items, const float* g, float grad_scale,
+                   float* partial, hipStream_t st);
 // LARS (optim.hip LarsArgs, optim/lars.py): ``lars_side`` non-null selects the LARS instantiation
 // of ddp_sgd_pack — int2 per work item {parameter | -1, first item of its tensor}, ``lars_tensors``
 // int4 per parameter {first global chunk, chunks, adapted, -}, ``lars_partial`` float2 per global

@@ -186,11 +186,20 @@ __device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper
   }
 }
 
-template <bool LARS>
+// Gradient guard of the clipped instantiations (ClipArgs below): this step's verdict, the same
+// in every block of the launch.
+struct GuardState {
+  float norm, c;  // sqrt(sum (g * grad_scale)^2) over every parameter element; clip coefficient
+  int skipped;    // non-finite norm with skip_nonfinite: the launch only clears the gradients
+  float* stats;   // {norm, c, skipped steps (uint32), -}, stored by block 0
+  int count;      // this launch ends the step: a skipped step is counted
+};
+
+template <bool LARS, bool GUARD = false>
 __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* __restrict__ descs,
                               float* __restrict__ p, float* __restrict__ g,
                               float* __restrict__ buf, const SgdHyper& h, float* tile,
-                              float trust);
+                              float trust, GuardState gd = GuardState{});
 
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
                                                        const long long* __restrict__ descs,
@@ -278,7 +287,10 @@ __global__ __launch_bounds__(256) void lars_norms_kernel(const int4* __restrict_
 
 // This block's trust ratio (1.0: excluded tensor, zero norm, item without an update). Every
 // condition but the partial loop's trip count is uniform over the block.
-__device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd) {
+// GUARD (the clipped instantiation): clip first — the gradient norm is that of the clipped
+// gradient, c * gn, with no second pass: sum (g gs c)^2 = c^2 * sum (g gs)^2.
+template <bool GUARD = false>
+__device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd, float c = 1.f) {
   __shared__ float s_trust;
   if (threadIdx.x < 64) {
     const int2 sd = a.side[blockIdx.x];
@@ -292,7 +304,9 @@ __device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd) {
           sp += v.x;
           sg += v.y;
         }
-        const float wn = sqrtf(wave_sum(sp)), gn = sqrtf(wave_sum(sg));
+        const float wn = sqrtf(wave_sum(sp));
+        float gn = sqrtf(wave_sum(sg));
+        if constexpr (GUARD) gn *= c;
         if (wn > 0.f && gn > 0.f) t = a.eta * wn / (gn + wd * wn + a.eps);
       }
       if (sd.y && threadIdx.x == 0) a.trust[sd.x] = t;
@@ -317,15 +331,154 @@ __global__ __launch_bounds__(256) void lars_pack_kernel(const int4* __restrict__
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
-template <bool LARS>
+// ---------------------------------------------------------------------------------------------
+// Gradient clipping and non-finite step skipping (optim/sgd.py max_grad_norm / skip_nonfinite).
+// The update launch consumes and clears the gradient in one pass and runs inside a replayed
+// graph, so the guard lives here, in two launches like LARS:
+//   1) grad_sumsq_kernel: one block per 8192-element chunk of every parameter (the chunking and
+//      the whole-arena chunk numbers of lars_norms_kernel) stores sum (g * grad_scale)^2 of its
+//      chunk: half the bytes of the LARS norms pass, no float atomics;
+//   2) the clipped instantiations of the fused update: wave 0 of every block sums ALL partials of
+//      the arena in one fixed order (lane l adds chunks l, l + 64, ... serially, then wave_sum) —
+//      every block of every launch gets the same bits —
+//          norm = sqrt(S);  c = min(1, max_norm / (norm + eps)) (1 without a max_norm)
+//      and the body runs with grad_scale * c. c == 1.0 reproduces the plain update bit for bit.
+//      A norm that is not finite (an Inf / NaN gradient, or S beyond fp32) with skip_nonfinite
+//      set: item kinds 0-3 only clear their gradient range (with zero_grad; a stale NaN would
+//      poison every later step, the kernels accumulate into the arena), kinds 4 and 5 run as they
+//      are; the data cursor, the completion signal and the schedule staging go on as in any
+//      step. The ``skip`` word keeps precedence: with it set nothing is touched or recorded.
+struct ClipArgs {
+  const float* partial;  // per global chunk: sum (g * grad_scale)^2 (grad_sumsq_kernel)
+  int n_chunks;          // chunks of the whole arena
+  float max_norm, eps;
+  int flags;             // 1: clip to max_norm, 2: skip a non-finite step, 4: count a skipped step
+  float* stats;          // GuardState::stats
+};
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const int4* __restrict__ items,
+                                                         const float* __restrict__ g,
+                                                         float grad_scale,
+                                                         float* __restrict__ partial) {
+  // {arena offset (multiple of 4), count <= kNormChunk, global chunk number, -}
+  const int4 it = items[blockIdx.x];
+  const size_t off = (size_t)(unsigned)it.x;
+  const int cnt = it.y, n4 = cnt >> 2;
+  const int tid = threadIdx.x;
+  const float4* g4 = reinterpret_cast<const float4*>(g + off);
+  constexpr int kIter = kNormChunk / (256 * 4);
+  float4 gv[kIter];
+#pragma unroll
+  for (int j = 0; j < kIter; ++j) {  // every 16-byte load of the chunk in flight at once
+    const int i = tid + 256 * j;
+    gv[j] = i < n4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float sg = 0.f;  // one serial fma chain per thread: 4 * kIter (+ 1 tail) terms
+#pragma unroll
+  for (int j = 0; j < kIter; ++j) {
+    const float* gg = &gv[j].x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gs = gg[e] * grad_scale;
+      sg = __builtin_fmaf(gs, gs, sg);
+    }
+  }
+  const int t = (n4 << 2) + tid;  // scalar tail: numel not a multiple of 4
+  if (t < cnt) {
+    const float gs = g[off + t] * grad_scale;
+    sg = __builtin_fmaf(gs, gs, sg);
+  }
+  sg = wave_sum(sg);
+  __shared__ float s_w[4];
+  if ((tid & 63) == 0) s_w[tid >> 6] = sg;
+  __syncthreads();
+  if (tid == 0) partial[it.z] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+// This step's verdict, computed by wave 0 of every block from the same partials in the same
+// order and broadcast through LDS (as lars_trust_block).
+__device__ __forceinline__ GuardState clip_block(const ClipArgs& a) {
+  __shared__ float s_norm, s_c;
+  __shared__ int s_skipped;
+  if (threadIdx.x < 64) {
+    float s = 0.f;
+    for (int c = threadIdx.x; c < a.n_chunks; c += 64) s += a.partial[c];
+    const float norm = sqrtf(wave_sum(s));
+    float c = 1.f;
+    if (a.flags & 1) {
+      const float q = a.max_norm / (norm + a.eps);
+      c = q >= 1.f ? 1.f : q;  // a NaN norm gives a NaN coefficient, as the arithmetic says
+    }
+    if (threadIdx.x == 0) {
+      s_norm = norm;
+      s_c = c;
+      s_skipped = ((a.flags & 2) && !(norm <= 3.402823466e+38f)) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  return GuardState{s_norm, s_c, s_skipped, a.stats, (a.flags & 4) ? 1 : 0};
+}
+
+// A skipped step's share of a work item of kind 0-3: its gradient range, cleared.
+__device__ __forceinline__ void guard_clear(const int4& it, const long long* __restrict__ descs,
+                                            float* __restrict__ g) {
+  const int tid = threadIdx.x;
+  if (it.x == 0 || it.x == 3) {
+    float* gp = g + (size_t)(unsigned)it.y;
+    for (int i = tid; i < it.z; i += 256) gp[i] = 0.f;
+    return;
+  }
+  if (it.x == 2) {
+    float* gp = g + (size_t)descs[12 * it.w] + (unsigned)it.y;
+    for (int i = tid; i < it.z; i += 256) gp[i] = 0.f;
+    return;
+  }
+  const long long* d = descs + 12 * it.y;  // kind 1: the tile's real channels (as the body)
+  const size_t poff = (size_t)d[0];
+  const int K = (int)d[1], Cr = (int)d[2], RS = (int)d[4] * (int)d[5];
+  int TK, TC;
+  tile_dims(RS, &TK, &TC);
+  const int k0 = it.z, c0 = it.w;
+  const int tk = min(TK, K - k0);
+  const int tcr = max(0, min(TC, Cr - c0));
+  if (d[8] == 0) {
+    const int run = tcr * RS;
+    for (int idx = tid; idx < tk * run; idx += 256) {
+      const int kl = idx / run, e = idx - kl * run;
+      g[poff + (size_t)(k0 + kl) * Cr * RS + (size_t)c0 * RS + e] = 0.f;
+    }
+  } else {
+    for (int idx = tid; idx < tk * RS * tcr; idx += 256) {
+      const int cl = idx % tcr, t = idx / tcr;
+      const int rs = t % RS, kl = t / RS;
+      g[poff + ((size_t)(k0 + kl) * RS + rs) * Cr + c0 + cl] = 0.f;
+    }
+  }
+}
+
+template <bool LARS, bool GUARD>
 __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* __restrict__ descs,
                               float* __restrict__ p, float* __restrict__ g,
                               float* __restrict__ buf, const SgdHyper& h, float* tile,
-                              float trust) {
+                              float trust, GuardState gd) {
   const int4 it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
   if (block_skip(h.skip)) return;
+  if constexpr (GUARD) {
+    if (blockIdx.x == 0 && tid == 0) {  // behind the skip word: a timed-out step records nothing
+      gd.stats[0] = gd.norm;
+      gd.stats[1] = gd.c;
+      if (gd.skipped && gd.count) {
+        unsigned* n = reinterpret_cast<unsigned*>(gd.stats + 2);
+        *n = *n + 1u;
+      }
+    }
+    if (gd.skipped && it.x != 4 && it.x != 5) {
+      if (h.zero_grad) guard_clear(it, descs, g);
+      return;
+    }
+  }
   if (it.x == 0) {
     const size_t off = (size_t)(unsigned)it.y;
     const int cnt = it.z;
@@ -489,6 +642,40 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
   }
 }
 
+// The clipped instantiations of the two kernels above (ClipArgs): the same launch, body and
+// arguments, run with grad_scale * c.
+__global__ __launch_bounds__(256) void sgd_clip_pack_kernel(const int4* __restrict__ items,
+                                                            const long long* __restrict__ descs,
+                                                            float* __restrict__ p,
+                                                            float* __restrict__ g,
+                                                            float* __restrict__ buf, SgdHyper h,
+                                                            ClipArgs ca) {
+  __shared__ float tile[kTileElems];
+  h.lr = sched_lr_block(h.sched, h.lr);
+  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
+  const GuardState gd = clip_block(ca);
+  h.grad_scale *= gd.c;
+  sgd_pack_body<false, true>(items, descs, p, g, buf, h, tile, 1.f, gd);
+  if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
+}
+
+__global__ __launch_bounds__(256) void lars_clip_pack_kernel(const int4* __restrict__ items,
+                                                             const long long* __restrict__ descs,
+                                                             float* __restrict__ p,
+                                                             float* __restrict__ g,
+                                                             float* __restrict__ buf, SgdHyper h,
+                                                             LarsArgs la, ClipArgs ca) {
+  __shared__ float tile[kTileElems];
+  h.lr = sched_lr_block(h.sched, h.lr);
+  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
+  const GuardState gd = clip_block(ca);
+  // (a skipped step leaves the stored ratios as they are)
+  const float trust = gd.skipped ? 1.f : lars_trust_block<true>(la, h.wd, gd.c);
+  h.grad_scale *= gd.c;
+  sgd_pack_body<true, true>(items, descs, p, g, buf, h, tile, trust, gd);
+  if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
+}
+
 // Tail of a pipelined step with sharded buckets (parallel/zero.py ShardedBf16Update.tail): one
 // block per segment copies gathered small-tensor values (fp32 send slots of every rank) into
 // the fp32 parameter arena; the last block to finish re-packs the bf16 operand copies of the
@@ -585,20 +772,42 @@ extern "C" int ddp_sgd_pack(const void* items, int n_items, const long long* des
                             unsigned* done, unsigned* signal, LrSched* sched, int sched_advance,
                             const void* lars_side, const void* lars_tensors,
                             const void* lars_partial, float* lars_trust, float lars_eta,
-                            float lars_eps, hipStream_t st) {
+                            float lars_eps, const float* clip_partial, int clip_chunks,
+                            float clip_max_norm, float clip_eps, int clip_flags,
+                            float* clip_stats, hipStream_t st) {
   SgdHyper h{lr, momentum, wd, grad_scale, nesterov, zero_grad, counter, delta, skip, shadow, slot,
              done, signal, sched, sched && sched_advance ? 1 : 0};
   if (n_items <= 0) return 0;
+  if (clip_partial && (!clip_stats || clip_chunks < 0)) return -1;
+  ClipArgs ca{clip_partial, clip_chunks, clip_max_norm, clip_eps, clip_flags, clip_stats};
   if (lars_side) {
     if (!lars_tensors || !lars_partial || !lars_trust) return -1;
     LarsArgs la{(const int2*)lars_side, (const int4*)lars_tensors, (const float2*)lars_partial,
                 lars_trust, lars_eta, lars_eps};
+    if (clip_partial) {
+      hipLaunchKernelGGL(lars_clip_pack_kernel, dim3(n_items), dim3(256), 0, st,
+                         (const int4*)items, descs, p, g, buf, h, la, ca);
+      return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(lars_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items,
                        descs, p, g, buf, h, la);
     return (int)hipGetLastError();
   }
+  if (clip_partial) {
+    hipLaunchKernelGGL(sgd_clip_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items,
+                       descs, p, g, buf, h, ca);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(sgd_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, descs,
                      p, g, buf, h);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ddp_grad_sumsq(const void* items, int n_items, const float* g, float grad_scale,
+                              float* partial, hipStream_t st) {
+  if (n_items <= 0) return 0;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, g,
+                     grad_scale, partial);
   return (int)hipGetLastError();
 }
 

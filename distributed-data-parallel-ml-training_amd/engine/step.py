@@ -261,6 +261,13 @@ class SegmentedDDPStep(TrainStep):
     BatchNorm-buffer broadcast inside g[0]); all of them sit on one stream, so they are
     serialised like the reference DDP's buckets (/root/reference/part3/main.py:174).
 
+    With the optimizer's gradient guard (optim/sgd.py ``max_grad_norm`` / ``skip_nonfinite``)
+    on the all-reduce plan no bucket is updated on its own: each bucket's all-reduce is followed
+    by its share of the sum-of-squares pass (comm stream, hidden like the collective), and ONE
+    whole-arena update launch follows the last bucket's, with the ``skip`` word, the cursor
+    advance, the D signal and the schedule staging. The price: the update is no longer hidden
+    under the backward. The sharded plans refuse such an optimizer.
+
     The DDP wrapper's own reducer is bypassed (``no_sync``). World size 1 has no collective
     unless ``emulate`` > 0 (bucket-sized stand-in passes) or ``emulate_gbps`` > 0 (a 32-CU
     stand-in lasting bytes / emulate_gbps that then multiplies the bucket by ``emulate_scale``:
@@ -342,10 +349,15 @@ class SegmentedDDPStep(TrainStep):
                              f"{len(self.buckets)} buckets")
         self.update = update
         if getattr(optimizer, "needs_whole_tensors", False) and (zero or "s16" in update):
-            # the sharded updates hand each rank a slice of a tensor: no per-tensor norm (LARS)
-            raise ValueError(f"{type(optimizer).__name__} needs whole tensors: the sharded "
-                             "updates (zero=True, \"s16\" buckets) split them across ranks; "
-                             "use update=\"allreduce\"")
+            # the sharded updates hand each rank a slice of a tensor: no per-tensor norm (LARS),
+            # no norm of the whole gradient without one more collective (the gradient guard)
+            raise ValueError(f"{type(optimizer).__name__} needs whole tensors"
+                             + (" (gradient clipping / non-finite step skipping takes the norm "
+                                "of the whole gradient; after a reduce-scatter a rank holds "
+                                "only a shard of it)"
+                                if getattr(optimizer, "guarded", False) else "")
+                             + ": the sharded updates (zero=True, \"s16\" buckets) split them "
+                             "across ranks; use update=\"allreduce\"")
         self.zero = None
         self.shard16 = None
         if zero:
@@ -521,6 +533,20 @@ class SegmentedDDPStep(TrainStep):
             return
         with trace_range(f"sync_bucket{j}"):
             self._allreduce(lo, hi, cs, self.comm_a)
+        if getattr(self.optimizer, "guarded", False):
+            # gradient guard: bucket j's share of the sum of squares runs behind its all-reduce
+            # (overlapped with the backward like the collective); no element may move before
+            # the norm of the whole gradient exists, so ONE whole-arena update follows the last
+            # bucket, carrying what the last bucket's launch carries otherwise
+            with trace_range(f"grad_sumsq_bucket{j}"):
+                self.optimizer.grad_sumsq(params=(i0, i1), stream=cs)
+            if last:
+                with trace_range("optimizer"):
+                    self.optimizer.step(zero_grad=True, stream=cs, skip=self._fp(4),
+                                        counter=self.loader.cursor_advance(),
+                                        signal=(self._fp(5), self._fp(1)), lr_advance="stage",
+                                        norm_done=True)
+            return
         with trace_range(f"optimizer_bucket{j}"):
             # a timed-out wait (error word set) skips the update: never apply gradients whose
             # bucket was not averaged

@@ -36,6 +36,16 @@ def _scheduled_lr(optimizer):
     return {"lr": optimizer.current_lr()}
 
 
+def _guard_stats(optimizer):
+    """Extra metrics fields of one iteration with the optimizer's gradient guard on (optim/sgd.py
+    max_grad_norm / skip_nonfinite): the gradient norm, the clip coefficient and the skipped
+    steps so far. Device reads: call after the iteration's synchronize."""
+    if not getattr(optimizer, "guarded", False):
+        return {}
+    return {"grad_norm": float(optimizer.grad_norm()), "clip_coef": float(optimizer.clip_coef()),
+            "skipped": int(optimizer.skipped_steps())}
+
+
 def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", sync=None,
                 log=print, metrics=None, watchdog=None, rank=0):
     running_loss = 0.0
@@ -73,7 +83,8 @@ def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", 
             log(f'Total time for 1-39 iteration in ns: {total_time}')
             log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
         if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr)
+            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr,
+                        **_guard_stats(optimizer))
         if watchdog is not None:
             watchdog.beat()
     stats["total_1_39_ns"] = total_time
@@ -116,7 +127,8 @@ def train_model_graph(step, train_loader, epoch, log=print, metrics=None, watchd
             log(f'Total time for 1-39 iteration in ns: {total_time}')
             log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
         if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr)
+            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr,
+                        **_guard_stats(step.optimizer))
         if watchdog is not None:
             watchdog.beat()
     if hasattr(step, "check_error"):

@@ -28,6 +28,11 @@ What LARS cannot do: an update that runs before the whole gradient exists (SGD i
 or that sees only a shard of a tensor (ZeRO-1, the bf16-gather sharded update) has no norm to
 use. Those paths refuse this optimizer; the all-reduce update (``update="allreduce"``) is the
 one to use.
+
+With the gradient guard of FusedSGD (``max_grad_norm``, ``skip_nonfinite``; optim/sgd.py): clip
+first. The ratio takes c * gn as the gradient norm (sum (g gs c)^2 = c^2 sum (g gs)^2: no
+second pass over the gradient) and the update runs with gs * c. Launch order: sum of squares,
+LARS norms, the clipped LARS update.
 """
 import torch
 
@@ -43,11 +48,13 @@ class LARS(FusedSGD):
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, grad_scale=1.0, trust_coefficient=0.001, eps=1e-8,
-                 exclude_1d=True):
+                 exclude_1d=True, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False):
         if dampening != 0.0:
             raise ValueError("LARS supports dampening=0 only")
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening,
-                         weight_decay=weight_decay, nesterov=nesterov, grad_scale=grad_scale)
+                         weight_decay=weight_decay, nesterov=nesterov, grad_scale=grad_scale,
+                         max_grad_norm=max_grad_norm, clip_eps=clip_eps,
+                         skip_nonfinite=skip_nonfinite)
         if len(self.param_groups) != 1:
             raise ValueError("LARS supports a single param group")
         hyper = {"trust_coefficient": float(trust_coefficient), "eps": float(eps),
@@ -135,7 +142,8 @@ class LARS(FusedSGD):
 
     # ---------------------------------------------------------------------------------- step
     @torch.no_grad()
-    def _cpu_step(self, params):
+    def _cpu_step(self, params, c=None):
+        """``c``: the guard's clip coefficient (fp32 tensor) or None."""
         g = self.param_groups[0]
         lr = self._cpu_lr()
         m, wd, nesterov = float(g["momentum"]), float(g["weight_decay"]), bool(g["nesterov"])
@@ -147,10 +155,14 @@ class LARS(FusedSGD):
             if p.grad is None:
                 continue
             gr = p.grad * gs
+            if c is not None:  # clip first: the update runs with gs * c ...
+                gr = p.grad * (torch.tensor(gs, dtype=torch.float32) * c)
             d = gr.add(p, alpha=wd)
             t = torch.ones((), dtype=torch.float32)
             if adapted[i]:
-                wn, gn = p.pow(2).sum().sqrt(), gr.pow(2).sum().sqrt()
+                wn, gn = p.pow(2).sum().sqrt(), (p.grad * gs).pow(2).sum().sqrt()
+                if c is not None:  # ... and the ratio takes c * gn
+                    gn = c * gn
                 if wn > 0 and gn > 0:
                     t = eta * wn / (gn + wd * wn + eps)
             trust[i] = t
@@ -166,16 +178,21 @@ class LARS(FusedSGD):
 
     @torch.no_grad()
     def step(self, closure=None, zero_grad=False, counter=None, skip=None, params=None,
-             stream=None, fused_taken=False, signal=None, lr_advance=None):
+             stream=None, fused_taken=False, signal=None, lr_advance=None, norm_done=False):
         """FusedSGD.step with the trust ratios: one norms launch over the adapted tensors of
-        the range, then the update launch (same arguments, same captured behaviour)."""
+        the range, then the update launch (same arguments, same captured behaviour). With the
+        gradient guard the sum-of-squares launch comes first (``norm_done`` as in FusedSGD)."""
         if fused_taken:
             raise RuntimeError("LARS: no update is taken in the backward (fused_taken)")
         if lr_advance is None:
             lr_advance = params is None
         if not self._fused:
             out = closure() if closure is not None else None
-            self._cpu_step(params)
+            c, skipped = self._cpu_guard(lr_advance) if self.guarded else (None, False)
+            if skipped:
+                self._cpu_lr()
+            else:
+                self._cpu_step(params, c)
             if lr_advance:
                 self.count_step()
             if zero_grad:
@@ -191,6 +208,8 @@ class LARS(FusedSGD):
         tensors = self._tensor_table()
         nitems, n_norm = self._norm_table(rng)
         gs = float(self._grad_scale_factor)
+        if self.guarded and not norm_done:
+            self.grad_sumsq(params, stream)
         if n_norm:
             native().lars_norms(nitems.data_ptr(), n_norm, a.data.data_ptr(), a.grad.data_ptr(),
                                 gs, self._lars_partial.data_ptr(), s)
@@ -208,7 +227,7 @@ class LARS(FusedSGD):
                           lars_partial=self._lars_partial.data_ptr(),
                           lars_trust=self._lars_trust.data_ptr(),
                           lars_eta=float(g["trust_coefficient"]), lars_eps=float(g["eps"]),
-                          **self._sched_kw(lr_advance))
+                          **self._sched_kw(lr_advance), **self._clip_kw(lr_advance))
         self._sched_commit(lr_advance, s)
         return None
 

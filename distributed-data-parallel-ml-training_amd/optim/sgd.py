@@ -14,11 +14,39 @@ table's step word advances once per training step: the launch that ends the step
 next index and a later launch makes it current (the engine's next batch launch, or a one-thread
 launch right behind the update). On the CPU the same fp32 value is written to
 ``param_groups[0]["lr"]`` before each step.
+
+Gradient guard (``max_grad_norm``, ``skip_nonfinite``; opt-in, all fp32, ``gs`` = ``grad_scale``):
+
+    S    = sum over every parameter element of (g * gs)^2        (arena padding excluded)
+    norm = sqrt(S)
+    c    = min(1, max_grad_norm / (norm + clip_eps))   if max_grad_norm is set, else 1
+    every update uses gs * c where it used gs          (c == 1.0: today's update bit for bit)
+
+and with ``skip_nonfinite`` a step whose norm is not finite (an Inf / NaN gradient, or S beyond
+fp32) changes no master, no momentum and no bf16 operand copy; it still clears the gradients
+(``zero_grad``), advances the data cursor and the schedule, gives the completion signal, and is
+counted (``skipped_steps()``). Without ``skip_nonfinite`` a non-finite norm gives c = 0 or NaN
+as the arithmetic says. The captured step has no place between ``backward()`` and ``step()``
+where ``clip_grad_norm_`` could stand, so on the GPU the guard lives in the update launch
+(csrc/kernels/optim.hip): ``grad_sumsq_kernel`` stores one partial sum per 8192-element chunk,
+and the clipped instantiation of the fused update sums all of them in a fixed order in every
+block's prologue — no float atomics, no host sync, nothing baked in at capture. An optimizer
+with the guard needs the whole gradient before any element moves: no SGD in the backward, no
+sharded update (after a reduce-scatter a rank holds a shard of the gradient only, and the
+global norm would need one more collective); ``update="allreduce"`` is the plan to use. On the
+CPU the norm is taken in fp64 and rounded once to fp32 (the oracle of the kernels), the
+gradients are multiplied by gs * c in place and torch.optim.SGD does the rest (the unguarded
+CPU path is torch.optim.SGD as is and, as before, does not apply ``grad_scale``).
 """
 import torch
 
 from .arena import arena_for
 from .schedule import LRSchedule
+
+_GUARD_SHARDED = ("gradient clipping / non-finite step skipping needs the norm of the whole "
+                  "gradient: after a reduce-scatter a rank holds only a shard of it, and a global "
+                  "norm would need one more collective; use the replicated update, "
+                  "update=\"allreduce\"")
 
 
 class FusedSGD(torch.optim.SGD):
@@ -27,7 +55,8 @@ class FusedSGD(torch.optim.SGD):
     needs_whole_tensors = False
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
-                 nesterov=False, grad_scale=1.0):
+                 nesterov=False, grad_scale=1.0, max_grad_norm=None, clip_eps=1e-6,
+                 skip_nonfinite=False):
         params = list(params)
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening,
                          weight_decay=weight_decay, nesterov=nesterov)
@@ -47,6 +76,143 @@ class FusedSGD(torch.optim.SGD):
         self._schedule = None
         self._lr_step = 0    # host mirror of the device step word: steps taken so far
         self._lr_dev = None  # device LrSched: int32 [step, n, next, pad] + n fp32 rates
+        self._guard_dev = None
+        self._guard_cpu = [float("nan"), 1.0, 0]  # norm, coefficient, skipped steps
+        self._set_guard(max_grad_norm, clip_eps, skip_nonfinite)
+
+    # ------------------------------------------------------------------------ gradient guard
+    CHUNK = 8192  # elements per sum-of-squares block (optim.hip kNormChunk; the items' chunking)
+
+    def _set_guard(self, max_grad_norm, clip_eps, skip_nonfinite):
+        """Set the guard's options (constructor, load_state_dict). They live in
+        ``param_groups[0]`` only when one of them is on: a plain optimizer's state_dict is what
+        it was. GPU: the partial and statistics buffers are allocated ONCE, so their addresses
+        survive re-captures; the options are launch arguments (capture after changing them)."""
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive")
+        if float(clip_eps) < 0.0:
+            raise ValueError("clip_eps must be >= 0")
+        on = max_grad_norm is not None or bool(skip_nonfinite)
+        g = self.param_groups[0] if self.param_groups else {}
+        if on:
+            hyper = {"max_grad_norm": None if max_grad_norm is None else float(max_grad_norm),
+                     "clip_eps": float(clip_eps), "skip_nonfinite": bool(skip_nonfinite)}
+            self.defaults.update(hyper)
+            g.update(hyper)
+            # the norm of the WHOLE gradient comes before any element's update
+            self.needs_whole_tensors = True
+        else:
+            for k in ("max_grad_norm", "clip_eps", "skip_nonfinite"):
+                g.pop(k, None)
+                self.defaults.pop(k, None)
+            self.__dict__.pop("needs_whole_tensors", None)
+        if on and self._fused and self._guard_dev is None:
+            a, dev = self.arena, self.arena.data.device
+            self._chunk0, c = [], 0  # first chunk of each parameter, numbered over the arena
+            for n in a.numels:
+                self._chunk0.append(c)
+                c += -(-n // self.CHUNK)
+            self._n_chunks = c
+            self._sumsq_partial = torch.zeros(max(c, 1), dtype=torch.float32, device=dev)
+            self._guard_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+            self._guard_dev[1] = 1.0
+            self._sumsq_tables = {}
+
+    @property
+    def guarded(self):
+        """Either guard option is on (the update launch is the clipped instantiation)."""
+        g = self.param_groups[0]
+        return g.get("max_grad_norm") is not None or bool(g.get("skip_nonfinite", False))
+
+    def grad_norm(self):
+        """2-norm of the last step's scaled gradient, before clipping (GPU: a view of the
+        device statistics the update launch writes; no sync)."""
+        if self._guard_dev is not None:
+            return self._guard_dev[0]
+        return torch.tensor(self._guard_cpu[0], dtype=torch.float32)
+
+    def clip_coef(self):
+        """Clip coefficient c of the last step (1.0: not clipped)."""
+        if self._guard_dev is not None:
+            return self._guard_dev[1]
+        return torch.tensor(self._guard_cpu[1], dtype=torch.float32)
+
+    def skipped_steps(self):
+        """Steps skipped for a non-finite gradient norm so far."""
+        if self._guard_dev is not None:
+            return self._guard_dev.view(torch.int32)[2]
+        return torch.tensor(self._guard_cpu[2], dtype=torch.int32)
+
+    def _sumsq_table(self, rng):
+        """Work items of the sum-of-squares launch over parameters [i0, i1): one per chunk,
+        {arena offset, count, global chunk number, -}; cached per range."""
+        t = self._sumsq_tables.get(rng)
+        if t is None:
+            a = self.arena
+            rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c, 0]
+                    for i in range(*rng)
+                    for c, s0 in enumerate(range(0, a.numels[i], self.CHUNK))]
+            t = (torch.tensor(rows, dtype=torch.int32, device=a.data.device) if rows else None,
+                 len(rows))
+            self._sumsq_tables[rng] = t
+        return t
+
+    def grad_sumsq(self, params=None, stream=None):
+        """Launch the sum-of-squares pass over parameters ``params = (i0, i1)`` (default: all)
+        on ``stream``: what ``step`` does first unless ``norm_done=True`` (the pipelined DDP step
+        runs it per bucket behind the bucket's all-reduce)."""
+        from ..ops.common import native, stream_handle
+        a = self.arena
+        rng = tuple(params) if params is not None else (0, len(a.params))
+        items, n = self._sumsq_table(rng)
+        if n:
+            native().grad_sumsq(items.data_ptr(), n, a.grad.data_ptr(),
+                                float(self._grad_scale_factor), self._sumsq_partial.data_ptr(),
+                                stream.cuda_stream if stream is not None else stream_handle())
+
+    def _clip_kw(self, count):
+        """Extra arguments of a native update launch: none without the guard (the launch is
+        then exactly the unguarded one). ``count``: the launch ends the step."""
+        if not self.guarded:
+            return {}
+        g = self.param_groups[0]
+        mx = g.get("max_grad_norm")
+        flags = (1 if mx is not None else 0) | (2 if g.get("skip_nonfinite") else 0) | \
+            (4 if count else 0)
+        return {"clip_partial": self._sumsq_partial.data_ptr(), "clip_chunks": self._n_chunks,
+                "clip_max_norm": float(mx) if mx is not None else 0.0,
+                "clip_eps": float(g.get("clip_eps", 1e-6)), "clip_flags": flags,
+                "clip_stats": self._guard_dev.data_ptr()}
+
+    @torch.no_grad()
+    def _cpu_guard(self, lr_advance):
+        """CPU: the guard's formula on the gradients of every parameter. Returns (c, skipped);
+        a skipped step is counted here."""
+        g = self.param_groups[0]
+        gs = float(self._grad_scale_factor)
+        grads = [p.grad for p in g["params"] if p.grad is not None]
+        # fp64 sum, rounded ONCE to fp32: the oracle of the kernels' fp32 sums
+        S = sum(((gr.double() * gs) ** 2).sum() for gr in grads) if grads else torch.zeros(())
+        S = torch.as_tensor(S, dtype=torch.float64).to(torch.float32)  # beyond fp32: inf
+        norm = S.sqrt()
+        c = torch.ones((), dtype=torch.float32)
+        if g.get("max_grad_norm") is not None:
+            q = torch.tensor(g["max_grad_norm"], dtype=torch.float32) / \
+                (norm + torch.tensor(g["clip_eps"], dtype=torch.float32))
+            c = torch.clamp(q, max=1.0)  # NaN stays NaN
+        skipped = bool(g.get("skip_nonfinite")) and not bool(torch.isfinite(norm))
+        self._guard_cpu[0], self._guard_cpu[1] = float(norm), float(c)
+        if skipped and lr_advance:
+            self._guard_cpu[2] += 1
+        return c, skipped
+
+    def _cpu_scale_grads(self, c):
+        """grad *= gs * c in place (what ``clip_grad_norm_`` does with c), unless it is 1."""
+        f = torch.tensor(float(self._grad_scale_factor), dtype=torch.float32) * c
+        if float(f) != 1.0:
+            for p in self.param_groups[0]["params"]:
+                if p.grad is not None:
+                    p.grad.mul_(f)
 
     # ------------------------------------------------------------------ learning-rate schedule
     def set_schedule(self, schedule, step=0):
@@ -155,6 +321,10 @@ class FusedSGD(torch.optim.SGD):
         in the WGRAD split-K finish that completes its gradient (conv_igemm.hip SgdFuse). Active
         until unregister_in_backward(); ``step(fused_taken=True)`` then skips the tensors whose
         finish took it (native sgd_fuse_taken)."""
+        if self.guarded:
+            raise RuntimeError("gradient clipping / non-finite step skipping cannot run in the "
+                               "backward: the norm exists only once the whole gradient does "
+                               "(TrainStep keeps opt_in_bwd False)")
         from ..ops.common import native
         a, g = self.arena, self.param_groups[0]
         nat = native()
@@ -286,6 +456,8 @@ class FusedSGD(torch.optim.SGD):
         torch.optim.SGD's exact per-element math on the flat slices on the CPU.
         ``lr_advance=False``: not the training step's last update (an attached schedule stays
         at this step for the launches that follow); ``"stage"``: as in ``step``."""
+        if self.guarded:
+            raise ValueError(_GUARD_SHARDED)
         g = self.param_groups[0]
         lr, m, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
         a = self.arena
@@ -341,7 +513,7 @@ class FusedSGD(torch.optim.SGD):
 
     @torch.no_grad()
     def step(self, closure=None, zero_grad=False, counter=None, skip=None, params=None,
-             stream=None, fused_taken=False, signal=None, lr_advance=None):
+             stream=None, fused_taken=False, signal=None, lr_advance=None, norm_done=False):
         """One fused launch. ``params = (i0, i1)``: only parameters i0 <= i < i1 (arena order);
         ``stream``: launch on this torch stream instead of the current one. ``zero_grad=True`` also clears every gradient after its use (the
         next step then needs no zero_grad fill); ``counter=(int32 device ptr, delta)`` is
@@ -354,11 +526,29 @@ class FusedSGD(torch.optim.SGD):
         it (default: a whole-arena step does, a ``params`` range does not — the pipelined step
         passes it for its last bucket). True: the launch stages the next step and a one-thread
         launch behind it makes it current; ``"stage"``: the caller's next batch launch does that
-        (``DeviceLoader.fill(lr_sched=...)``: no extra dispatch in an engine step)."""
+        (``DeviceLoader.fill(lr_sched=...)``: no extra dispatch in an engine step).
+        With the gradient guard the sum-of-squares launch over ``params`` runs first;
+        ``norm_done=True``: the caller already ran ``grad_sumsq`` over every parameter (the
+        update always sums the partials of the WHOLE arena). A skipped step is counted by the
+        launch that ends the step (``lr_advance``)."""
         if lr_advance is None:
             lr_advance = params is None
         if not self._fused:
             self._cpu_lr()
+            if self.guarded:
+                if closure is not None:  # the gradients come first
+                    with torch.enable_grad():
+                        loss = closure()
+                    closure = lambda: loss  # noqa: E731
+                c, skipped = self._cpu_guard(lr_advance)
+                if skipped:
+                    out = closure() if closure is not None else None
+                    if lr_advance:
+                        self.count_step()
+                    if zero_grad:
+                        super().zero_grad(set_to_none=False)
+                    return out
+                self._cpu_scale_grads(c)
             out = super().step(closure)
             if lr_advance:
                 self.count_step()
@@ -371,10 +561,14 @@ class FusedSGD(torch.optim.SGD):
         a = self.arena
         exclude = pack_only = frozenset()
         if fused_taken:
+            if self.guarded:
+                raise RuntimeError("gradient guard: no update is taken in the backward")
             pack_only = self._master_in_backward()
             exclude = self._fused_in_backward() | pack_only
         items, n_items, descs = self._work_table(params, exclude, pack_only)
         sched = self._sched_kw(lr_advance)
+        if self.guarded and not norm_done:
+            self.grad_sumsq(params, stream)
         if n_items == 0:  # every tensor was updated in the backward: only the data cursor
             if sched.get("sched_advance"):
                 native().counter_add(int(counter[0]) if counter else 0,
@@ -396,7 +590,8 @@ class FusedSGD(torch.optim.SGD):
                           delta=int(counter[1]) if counter else 0,
                           skip=int(skip) if skip else 0,
                           done=int(signal[0]) if signal else 0,
-                          signal=int(signal[1]) if signal else 0, **sched)
+                          signal=int(signal[1]) if signal else 0, **sched,
+                          **self._clip_kw(lr_advance))
         self._sched_commit(lr_advance, s)
         return None
 
@@ -404,6 +599,8 @@ class FusedSGD(torch.optim.SGD):
         sd = super().state_dict()
         if self._schedule is not None:  # plain ints / floats / lists: loads with weights_only
             sd["lr_schedule"] = {"schedule": self._schedule.state_dict(), "step": self._lr_step}
+        if self.guarded:
+            sd["grad_guard"] = {"skipped": int(self.skipped_steps())}
         if self._fused:
             # expose the momentum buffers in torch.optim.SGD's per-parameter layout
             a = self.arena
@@ -415,8 +612,18 @@ class FusedSGD(torch.optim.SGD):
         ls = sd.get("lr_schedule")
         if ls is not None:
             self.set_schedule(LRSchedule.from_state_dict(ls["schedule"]), step=int(ls["step"]))
+        saved = sd["param_groups"][0] if sd.get("param_groups") else {}
+        if "skip_nonfinite" in saved or "max_grad_norm" in saved:
+            self._set_guard(saved.get("max_grad_norm"), saved.get("clip_eps", 1e-6),
+                            saved.get("skip_nonfinite", False))
+        gg = sd.get("grad_guard")
+        if gg is not None and self.guarded:
+            if self._guard_dev is not None:
+                self._guard_dev.view(torch.int32)[2] = int(gg["skipped"])
+            self._guard_cpu[2] = int(gg["skipped"])
         if not self._fused:
-            return super().load_state_dict({k: v for k, v in sd.items() if k != "lr_schedule"})
+            return super().load_state_dict({k: v for k, v in sd.items()
+                                            if k not in ("lr_schedule", "grad_guard")})
         a = self.arena
         st = sd.get("state", {})
         for i, p in enumerate(a.params):

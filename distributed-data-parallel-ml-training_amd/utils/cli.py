@@ -78,17 +78,29 @@ def build_parser(description=None, distributed=True):
                         'linear scaling rule gives a large global batch (works inside --graph)')
     g.add_argument('--lars-eta', type=float, default=0.001, help='LARS trust coefficient')
     g.add_argument('--lars-eps', type=float, default=1e-8)
+    g.add_argument('--clip-grad-norm', type=float, default=None,
+                   help='clip the 2-norm of the whole gradient to this value inside the update '
+                        'launch (torch.nn.utils.clip_grad_norm_; works inside --graph); default off')
+    g.add_argument('--skip-nonfinite-grads', action='store_true',
+                   help='a step whose gradient norm is Inf / NaN changes no parameter and is '
+                        'counted instead (works inside --graph); default off')
     return p
 
 
 def optimizer_from_args(args, params, lr):
     """The run's optimizer: the reference's SGD(lr, 0.9, 1e-4), or LARS over the same
-    hyper-parameters with --optimizer lars (biases and BatchNorm vectors are not adapted)."""
+    hyper-parameters with --optimizer lars (biases and BatchNorm vectors are not adapted);
+    --clip-grad-norm / --skip-nonfinite-grads switch the gradient guard of either on."""
     from ..optim import FusedSGD, LARS
+    guard = {}
+    if getattr(args, "clip_grad_norm", None) is not None or \
+            getattr(args, "skip_nonfinite_grads", False):
+        guard = {"max_grad_norm": getattr(args, "clip_grad_norm", None),
+                 "skip_nonfinite": bool(getattr(args, "skip_nonfinite_grads", False))}
     if getattr(args, "optimizer", "sgd") == "lars":
         return LARS(params, lr=lr, momentum=0.9, weight_decay=0.0001,
-                    trust_coefficient=args.lars_eta, eps=args.lars_eps)
-    return FusedSGD(params, lr=lr, momentum=0.9, weight_decay=0.0001)
+                    trust_coefficient=args.lars_eta, eps=args.lars_eps, **guard)
+    return FusedSGD(params, lr=lr, momentum=0.9, weight_decay=0.0001, **guard)
 
 
 def lr_schedule_from_args(args, steps_per_epoch):
