@@ -636,8 +636,9 @@ PYBIND11_MODULE(_native, m) {
                       int L, int B, int H, int W, int Cp, int pad, int flip, unsigned int seed,
                       unsigned int epoch, std::vector<float> mean, std::vector<float> std_,
                       uintptr_t x, uintptr_t y, uintptr_t st, uintptr_t zero, size_t zero_n,
-                      uintptr_t sched) {
+                      uintptr_t sched, int cursor_off) {
     ddp_amd::AugArgs a{};
+    a.cursor_off = cursor_off;
     a.sched = P<ddp_amd::LrSched>(sched);
     a.zero = P<float>(zero);
     a.zero_n = zero ? zero_n : 0;
@@ -651,7 +652,7 @@ PYBIND11_MODULE(_native, m) {
      py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cp"), py::arg("pad"), py::arg("flip"),
      py::arg("seed"), py::arg("epoch"), py::arg("mean"), py::arg("std"), py::arg("x"),
      py::arg("y"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0,
-     py::arg("sched") = 0);
+     py::arg("sched") = 0, py::arg("cursor_off") = 0);
   m.def("nchw_to_nhwc", [](uintptr_t x, int N, int C, int H, int W, int Cp, uintptr_t out,
                            uintptr_t st) {
     check(ddp_nchw_to_nhwc(P<float>(x), N, C, H, W, Cp, P<void>(out), S(st)), "nchw_to_nhwc");

@@ -220,6 +220,8 @@ struct AugArgs {
   const int* labels;            // [Nd]
   const int* indices;           // [L] sample order for this rank/epoch
   const int* cursor;            // device batch counter (may be null -> 0)
+  int cursor_off;               // added to the counter: micro-batch j of an accumulated step reads
+                                //   batch cursor + j from one captured graph (engine/step.py)
   int L, B, H, W, Cp, pad, flip;
   uint32_t seed, epoch;
   float mean[3], inv_std[3];

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
     const int b = (int)(t / ((size_t)a.H * a.W));
     const int pix = (int)(t % ((size_t)a.H * a.W));
     const int oy = pix / a.W, ox = pix % a.W;
-    const int pos = (int)(((long long)cur * a.B + b) % a.L);
+    const int pos = (int)(((long long)(cur + a.cursor_off) * a.B + b) % a.L);
     const int idx = a.indices[pos];
     int cy = 0, cx = 0, fl = 0;
     if (a.pad > 0 || a.flip) {

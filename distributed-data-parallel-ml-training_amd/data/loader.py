@@ -139,7 +139,7 @@ class DeviceLoader:
         n = math.ceil(self.idx.numel() / self.batch_size)
         return min(n, self.max_batches) if self.max_batches else n
 
-    def _launch(self, x, y, indices_ptr, L, B, cursor_ptr, sched=0):
+    def _launch(self, x, y, indices_ptr, L, B, cursor_ptr, sched=0, offset=0):
         from ..ops.common import native, stream_handle, step_scratch
         pad, flip = (4, 1) if self.train else (0, 0)
         # the augment launch also clears the per-step BN-statistics scratch that the next
@@ -150,7 +150,8 @@ class DeviceLoader:
                          L, B, self.ds.height, self.ds.width, self.cpad, pad, flip,
                          self.ds.seed & 0xFFFFFFFF, self.epoch, CIFAR_MEAN, CIFAR_STD,
                          x.data_ptr(), y.data_ptr(), stream_handle(), zero=zp, zero_n=zn,
-                         **({"sched": sched} if sched else {}))
+                         **({"sched": sched} if sched else {}),
+                         **({"cursor_off": int(offset)} if offset else {}))
 
     def batch(self, start, B):
         """Materialise samples [start, start+B) of this rank's shard (new tensors)."""
@@ -177,24 +178,28 @@ class DeviceLoader:
             self._static = (x, y)
         return self._static
 
-    def fill(self, advance=True, lr_sched=0):
+    def fill(self, advance=True, lr_sched=0, offset=0):
         """Write the next batch (cursor-addressed, wraps around the shard) into the static
         buffers and advance the device cursor. Safe to capture into a hipGraph.
         ``advance=False`` leaves the increment to the caller (engine/step.py folds it into the
         optimizer launch: see ``cursor_advance``). ``lr_sched``: device learning-rate schedule
         (optim/sgd.py) whose step, staged by the previous step's optimizer launch, this launch
-        makes current — the batch launch is the first kernel of an engine step."""
+        makes current — the batch launch is the first kernel of an engine step.
+        ``offset``: read batch cursor + offset (baked into the launch: micro-batch j of an
+        accumulated step, whose K batch launches share one cursor that the step's last launch
+        advances by K)."""
         from ..ops.common import native, stream_handle
         x, y = self.static_batch()
         self._launch(x, y, self.idx.data_ptr(), self.idx.numel(), self.batch_size,
-                     self.cursor.data_ptr(), sched=lr_sched)
+                     self.cursor.data_ptr(), sched=lr_sched, offset=offset)
         if advance:
             native().counter_add(self.cursor.data_ptr(), 1, stream_handle())
         return x, y
 
-    def cursor_advance(self):
-        """(device pointer, delta) of the pending cursor increment after ``fill(advance=False)``."""
-        return (self.cursor.data_ptr(), 1)
+    def cursor_advance(self, k=1):
+        """(device pointer, delta) of the pending cursor increment after ``fill(advance=False)``;
+        ``k`` = batches consumed since the last advance (micro-batches of an accumulated step)."""
+        return (self.cursor.data_ptr(), int(k))
 
 
 def make_loader(dataset, batch_size, device, num_replicas=1, rank=0, train=True, shard=True,

@@ -95,9 +95,11 @@ def main(part, argv=None):
                 and hasattr(model.module, "forward_loss_split")):
             # each bucket's all-reduce + optimizer update on the comm stream while the earlier
             # layers' backward runs (engine/step.py SegmentedDDPStep)
-            step = SegmentedDDPStep(model, optimizer, criterion, train_loader, split=split)
+            step = SegmentedDDPStep(model, optimizer, criterion, train_loader, split=split,
+                                    accum_steps=args.accum_steps)
         else:
-            step = TrainStep(model, optimizer, criterion, train_loader, sync=sync)
+            step = TrainStep(model, optimizer, criterion, train_loader, sync=sync,
+                             accum_steps=args.accum_steps)
         step.warmup(2)
         step.capture()
         torch.cuda.synchronize()
@@ -118,11 +120,12 @@ def main(part, argv=None):
                 train_loader.set_epoch(epoch)
                 step.capture()  # the augmentation seed is a launch argument: new epoch, new graph
             train_model_graph(step, train_loader, epoch, metrics=metrics, watchdog=watchdog,
-                              rank=rank)
+                              rank=rank, accum_steps=args.accum_steps)
         else:
             train_loader.set_epoch(epoch)
             train_model(model, train_loader, optimizer, criterion, epoch, device, sync,
-                        metrics=metrics, watchdog=watchdog, rank=rank)
+                        metrics=metrics, watchdog=watchdog, rank=rank,
+                        accum_steps=args.accum_steps)
         if not args.no_test:
             test_model(model, test_loader, criterion, device, watchdog=watchdog)
 

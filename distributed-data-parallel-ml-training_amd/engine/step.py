@@ -10,12 +10,14 @@ replay it. Host cost per step becomes one graph launch.
 Capture protocol: a few eager warm-up steps on a side stream (lazy allocations, autograd
 structures), then ``torch.cuda.graph`` capture; replays are bit-identical to eager steps.
 """
+import contextlib
 import os
 
 import torch
 
 from ..parallel.comm import is_live
 from ..utils.trace import trace_range
+from .trainer import micro_batch_ctx
 
 
 def capture_mode():
@@ -54,11 +56,33 @@ def sgd_in_backward_ok(model):
     return comm is None or not is_live(comm)
 
 
+def accum_grad_scale(grad_scale, m):
+    """Gradient scale of the update that consumes the sum of ``m`` micro-batch gradients:
+    float32(grad_scale / m), rounded on the host — the value every update site multiplies the
+    accumulated gradient by (exact for m a power of two)."""
+    if m == 1:
+        return grad_scale
+    return float(torch.tensor(float(grad_scale) / m, dtype=torch.float32))
+
+
 class TrainStep:
-    def __init__(self, model, optimizer, criterion, loader, sync=None, use_graph=True):
+    """``accum_steps`` = K > 1 (gradient accumulation): one step consumes K consecutive loader
+    batches. Micro-steps 0..K-2 are batch launch (cursor offset j) + forward + backward into
+    the gradient arena, which every producer adds to; the last micro-step is the plain step on
+    batch cursor + K-1 with the update scaled by float32(grad_scale / K) and the cursor advanced
+    by K. All K are captured into the one graph. Every update runs in the step's own launch:
+    a WGRAD finish that takes the step in the backward steps from its own sum alone, and the
+    accumulating form of those finishes measured no faster than store + update launch
+    (profiles/grad_accum_ab.md), so SGD in the backward stays a K = 1 feature."""
+
+    def __init__(self, model, optimizer, criterion, loader, sync=None, use_graph=True,
+                 accum_steps=1):
         self.model, self.optimizer, self.criterion, self.loader = model, optimizer, criterion, loader
         self.sync = sync
         self.use_graph = use_graph
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError("accum_steps must be >= 1")
         dev = loader.device
         self.loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
         self._one = torch.ones((), dtype=torch.float32, device=dev)
@@ -77,7 +101,65 @@ class TrainStep:
         # LARS needs the norm of the whole gradient before any element moves: never in the backward.
         self.opt_in_bwd = (self.fold_opt and sync is None and sgd_in_backward_ok(model)
                            and hasattr(optimizer, "register_in_backward")
-                           and not getattr(optimizer, "needs_whole_tensors", False))
+                           and not getattr(optimizer, "needs_whole_tensors", False)
+                           and self.accum_steps == 1)
+        if self.accum_steps > 1 and not self.fold_opt:
+            raise ValueError("accum_steps > 1 needs the fused optimizer and the device loader "
+                             "(the update launch scales, clears and advances the cursor)")
+
+    @contextlib.contextmanager
+    def _scaled(self, m):
+        """The optimizer's grad_scale set to float32(grad_scale / m) for the launches issued
+        inside (a launch argument: baked into a capture)."""
+        if m == 1:
+            yield
+            return
+        opt = self.optimizer
+        base = opt.grad_scale_factor
+        opt.grad_scale_factor = accum_grad_scale(base, m)
+        try:
+            yield
+        finally:
+            opt.grad_scale_factor = base
+
+    def _accumulate(self, j):
+        """Micro-step j < K-1: batch cursor + j, forward, backward; no sync, no update."""
+        with micro_batch_ctx(self.model, j == 0, False):
+            with trace_range("data"):
+                x, y = self.loader.fill(advance=False, offset=j,
+                                        **(self._lr_sched() if j == 0 else {}))
+            with trace_range("forward"):
+                if self.fused:
+                    loss = self.model.forward_loss(x, y, acc=self.loss_sum, transient=True)
+                else:
+                    loss = self.criterion(self.model(x), y)
+            with trace_range("backward"):
+                loss.backward(self._one)
+        if not self.fused:
+            self.loss_sum.add_(loss.detach())
+
+    def _body_accum(self):
+        K = self.accum_steps
+        for j in range(K - 1):
+            self._accumulate(j)
+        with self._scaled(K), micro_batch_ctx(self.model, False, True):
+            with trace_range("data"):
+                x, y = self.loader.fill(advance=False, offset=K - 1)
+            with trace_range("forward"):
+                if self.fused:
+                    loss = self.model.forward_loss(x, y, acc=self.loss_sum, transient=True)
+                else:
+                    loss = self.criterion(self.model(x), y)
+            with trace_range("backward"):
+                loss.backward(self._one)
+            if self.sync is not None:
+                with trace_range("sync"):
+                    self.sync(self.model)
+            with trace_range("optimizer"):
+                self.optimizer.step(zero_grad=True, counter=self.loader.cursor_advance(K),
+                                    **({"lr_advance": "stage"} if self._lr_sched() else {}))
+        if not self.fused:
+            self.loss_sum.add_(loss.detach())
 
     def _fused_loss(self):
         """Use the model's fused classifier+loss when the criterion is the plain mean CE."""
@@ -87,6 +169,8 @@ class TrainStep:
                 and type(self.criterion) is CrossEntropyLoss)
 
     def _body(self):
+        if self.accum_steps > 1:
+            return self._body_accum()
         if not self.fold_opt:
             self.optimizer.zero_grad()
         if self.opt_in_bwd:
@@ -160,11 +244,19 @@ class TrainStep:
         else:
             self._body()
 
-    def tail_step(self, x, y):
+    def tail_step(self, x, y=None):
         """One EAGER step on an explicit batch of any size (the epoch's partial last batch,
         engine/trainer.py train_model_graph): forward, backward, gradient sync (DDP buckets via
         the wrapper's reducer; 2A/2B via ``sync``) and the optimizer, on the same stream as the
-        replays. Gradients are clear on entry when the optimizer launch clears them."""
+        replays. Gradients are clear on entry when the optimizer launch clears them.
+        ``tail_step([(x0, y0), (x1, y1), ...])``: the m micro-batches left over at the end of
+        an accumulated epoch as ONE optimizer step scaled by 1/m (each loss is the mean over
+        its own samples)."""
+        if y is None:
+            batches = list(x)
+            if len(batches) > 1:
+                return self._tail_accum(batches)
+            x, y = batches[0]
         if self._lr_sched():
             # no batch launch of the loader precedes this step: make the learning-rate step
             # that the last replay staged current before the backward reads it
@@ -187,6 +279,29 @@ class TrainStep:
             self.optimizer.step()
         if self.opt_in_bwd:
             self.optimizer.unregister_in_backward()
+
+    def _tail_accum(self, batches):
+        m = len(batches)
+        if not self.fold_opt:
+            raise ValueError("an accumulated step needs the fused optimizer and the device loader")
+        if self._lr_sched():
+            self.optimizer.commit_lr_step()
+        for j, (x, y) in enumerate(batches):
+            last = j == m - 1
+            with contextlib.ExitStack() as st:
+                st.enter_context(micro_batch_ctx(self.model, j == 0, last))
+                if last:
+                    st.enter_context(self._scaled(m))
+                if self.fused:
+                    loss = self.model.forward_loss(x, y, acc=self.loss_sum)
+                else:
+                    loss = self.criterion(self.model(x), y)
+                    self.loss_sum.add_(loss.detach())
+                loss.backward(self._one)
+                if last:
+                    if self.sync is not None:
+                        self.sync(self.model)
+                    self.optimizer.step(zero_grad=True)
 
     def wait(self, timeout_s=None, poll_s=0.001):
         """Synchronise with the device, optionally bounded: returns False on timeout instead of
@@ -273,14 +388,20 @@ class SegmentedDDPStep(TrainStep):
     stand-in lasting bytes / emulate_gbps that then multiplies the bucket by ``emulate_scale``:
     an optimizer that did not wait would miss it). Measurements: profiles/r1_segmented_overlap.md
     (single cut, v4) and profiles/r2_pipelined_ddp.md.
+
+    ``accum_steps`` = K > 1: micro-steps 0..K-2 run whole (forward, uncut backward, no
+    collective) at the front of segment 0's graph, after the D wait and the buffer broadcast;
+    the last micro-step is the cut / pipelined step, whose updates use float32(grad_scale / K)
+    and whose last launch advances the cursor by K.
     """
 
     WAIT_TIMEOUT_S = 100.0  # a device-side wait that exceeds this records an error and returns
 
     def __init__(self, ddp, optimizer, criterion, loader, split=4, emulate=0, emulate_gbps=0.0,
                  emulate_scale=1.0, grad_comm="fp32", zero=False, collectives=True,
-                 update="allreduce", emulate_world=8, emulate_passes=1):
-        super().__init__(ddp, optimizer, criterion, loader, sync=None, use_graph=True)
+                 update="allreduce", emulate_world=8, emulate_passes=1, accum_steps=1):
+        super().__init__(ddp, optimizer, criterion, loader, sync=None, use_graph=True,
+                         accum_steps=accum_steps)
         # every bucket's update runs on the comm stream after its collective: never in the
         # backward (an emulated or single-rank collective still has to see the gradients)
         self.opt_in_bwd = False
@@ -394,16 +515,20 @@ class SegmentedDDPStep(TrainStep):
         # events recorded on the comm stream around each bucket's collective + update
         self.probe = None
 
-    def tail_step(self, x, y):
-        """The epoch's partial last batch as one eager step. With a sharded update the masters
-        and momentum are authoritative only on their shard owners and the replicated update of
-        TrainStep.tail_step would diverge the replicas: refused (train full batches only, or
-        use the all-reduce plan)."""
+    def tail_step(self, x, y=None):
+        """The epoch's partial last batch (or leftover micro-batches) as one eager step. With a
+        sharded update the masters and momentum are authoritative only on their shard owners
+        and the replicated update of TrainStep.tail_step would diverge the replicas: refused
+        (train full batches only, or use the all-reduce plan)."""
         if self.shard16 is not None or self.zero is not None:
             raise RuntimeError("SegmentedDDPStep: a partial batch needs the all-reduce update "
                                "(the sharded update keeps masters / momentum on shard owners)")
         torch.cuda.current_stream().wait_stream(self.comm_stream)
         super().tail_step(x, y)
+
+    def _advance(self):
+        """The step's pending cursor increment: its K micro-batches."""
+        return self.loader.cursor_advance(self.accum_steps)
 
     def _probe_event(self, stream):
         ev = torch.cuda.Event(enable_timing=True)
@@ -441,9 +566,19 @@ class SegmentedDDPStep(TrainStep):
                            main.cuda_stream)
         if self.sync_buffers:
             self.ddp._sync_buffers()  # what DDP.forward would do (no-op without buffers / world 1)
+        K = self.accum_steps
         with self.ddp.no_sync():
+            for j in range(K - 1):  # accumulate-only micro-steps: whole, uncut, no collective
+                with trace_range("data"):
+                    x, y = self.loader.fill(advance=False, offset=j,
+                                            **(self._lr_sched() if j == 0 else {}))
+                with trace_range("forward"):
+                    loss = self.ddp.module.forward_loss(x, y, acc=self.loss_sum, transient=True)
+                with trace_range("backward"):
+                    loss.backward(self._one)
             with trace_range("data"):
-                x, y = self.loader.fill(advance=False, **self._lr_sched())
+                x, y = self.loader.fill(advance=False, offset=K - 1,
+                                        **(self._lr_sched() if K == 1 else {}))
             with trace_range("forward"):
                 loss, cuts = self.ddp.module.forward_loss_split(
                     x, y, self.split, acc=self.loss_sum, transient=True)
@@ -473,7 +608,8 @@ class SegmentedDDPStep(TrainStep):
         (i0, i1), (lo, hi) = self.buckets[j]
         last = j == len(self.buckets) - 1
         t0 = self._probe_event(cs) if self.probe is not None else None
-        self._comm_body(j, cs, i0, i1, lo, hi, last)
+        with self._scaled(self.accum_steps):
+            self._comm_body(j, cs, i0, i1, lo, hi, last)
         if t0 is not None:
             self.probe.append((j, t0, self._probe_event(cs)))
 
@@ -507,7 +643,7 @@ class SegmentedDDPStep(TrainStep):
                 self._standin_bucket = j
                 with trace_range(f"shard16_update_bucket{j}"):
                     self.shard16.step(j, stream=cs, skip=self._fp(4),
-                                      counter=self.loader.cursor_advance() if last else None,
+                                      counter=self._advance() if last else None,
                                       lr_advance="stage" if last else False,
                                       standin=self._standin(cs) if self.comm_a is None else None)
             else:
@@ -516,7 +652,7 @@ class SegmentedDDPStep(TrainStep):
                 with trace_range(f"optimizer_bucket{j}"):
                     self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs,
                                         skip=self._fp(4),
-                                        counter=self.loader.cursor_advance() if last else None,
+                                        counter=self._advance() if last else None,
                                         lr_advance="stage" if last else False)
             if last:  # small-tensor unpack + operand re-pack + signal D, one launch
                 with trace_range("shard16_tail"):
@@ -526,7 +662,7 @@ class SegmentedDDPStep(TrainStep):
         if self.zero is not None:
             with trace_range(f"zero_update_bucket{j}"):
                 self.zero.step(j, stream=cs, skip=self._fp(4),
-                               counter=self.loader.cursor_advance() if last else None,
+                               counter=self._advance() if last else None,
                                lr_advance="stage" if last else False)
             if last:
                 native().flag_signal(self._fp(1), cs.cuda_stream)
@@ -543,7 +679,7 @@ class SegmentedDDPStep(TrainStep):
             if last:
                 with trace_range("optimizer"):
                     self.optimizer.step(zero_grad=True, stream=cs, skip=self._fp(4),
-                                        counter=self.loader.cursor_advance(),
+                                        counter=self._advance(),
                                         signal=(self._fp(5), self._fp(1)), lr_advance="stage",
                                         norm_done=True)
             return
@@ -555,7 +691,7 @@ class SegmentedDDPStep(TrainStep):
             # the next step of an attached learning-rate schedule (lr_advance; the next step's
             # batch launch, which waits for D, makes it current)
             self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs, skip=self._fp(4),
-                                counter=self.loader.cursor_advance() if last else None,
+                                counter=self._advance() if last else None,
                                 signal=(self._fp(5), self._fp(1)) if last else None,
                                 lr_advance="stage" if last else False)
 

@@ -80,6 +80,19 @@ class FusedSGD(torch.optim.SGD):
         self._guard_cpu = [float("nan"), 1.0, 0]  # norm, coefficient, skipped steps
         self._set_guard(max_grad_norm, clip_eps, skip_nonfinite)
 
+    @property
+    def grad_scale_factor(self):
+        """The constructor's ``grad_scale``: the factor every update site multiplies the
+        gradient by before using it (a launch argument: set it before capturing). Gradient
+        accumulation over K micro-batches sets float32(grad_scale / K) for the step that
+        consumes the sum (engine/step.py). Not named ``grad_scale``: torch.optim.Optimizer
+        reads an attribute of that name as the AMP gradient scaler's tensor."""
+        return self._grad_scale_factor
+
+    @grad_scale_factor.setter
+    def grad_scale_factor(self, v):
+        self._grad_scale_factor = float(v)
+
     # ------------------------------------------------------------------------ gradient guard
     CHUNK = 8192  # elements per sum-of-squares block (optim.hip kNormChunk; the items' chunking)
 
@@ -320,7 +333,8 @@ class FusedSGD(torch.optim.SGD):
         bf16 copy has the master's index order to the kernel library, which applies its update
         in the WGRAD split-K finish that completes its gradient (conv_igemm.hip SgdFuse). Active
         until unregister_in_backward(); ``step(fused_taken=True)`` then skips the tensors whose
-        finish took it (native sgd_fuse_taken)."""
+        finish took it (native sgd_fuse_taken). Not with gradient accumulation: a finish takes
+        its step from its own sum alone (engine/step.py keeps opt_in_bwd False for K > 1)."""
         if self.guarded:
             raise RuntimeError("gradient clipping / non-finite step skipping cannot run in the "
                                "backward: the norm exists only once the whole gradient does "

@@ -340,6 +340,8 @@ class DistributedDataParallel(nn.Module):
 
     # ------------------------------------------------------------ per-step
     def _sync_buffers(self):
+        if not getattr(self, "_buffer_sync_enabled", True):
+            return
         if self.broadcast_buffers and is_live(self.comm) and torch.is_grad_enabled():
             if self._flat_buffers is None:
                 self._flatten_buffers()
@@ -394,6 +396,18 @@ class DistributedDataParallel(nn.Module):
             yield
         finally:
             self._sync_enabled = prev
+
+    @contextlib.contextmanager
+    def no_buffer_sync(self):
+        """Forward passes inside the context skip the buffer broadcast: micro-batches 1..K-1 of
+        an accumulated optimizer step (the buffers are broadcast once per step, before its first
+        micro-batch)."""
+        prev = getattr(self, "_buffer_sync_enabled", True)
+        self._buffer_sync_enabled = False
+        try:
+            yield
+        finally:
+            self._buffer_sync_enabled = prev
 
     def _queue_finalize(self):
         if not self._in_backward:

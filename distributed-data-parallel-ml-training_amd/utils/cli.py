@@ -84,7 +84,18 @@ def build_parser(description=None, distributed=True):
     g.add_argument('--skip-nonfinite-grads', action='store_true',
                    help='a step whose gradient norm is Inf / NaN changes no parameter and is '
                         'counted instead (works inside --graph); default off')
+    g.add_argument('--accum-steps', type=_accum_steps, default=1,
+                   help='gradient accumulation: one optimizer step consumes this many consecutive '
+                        'batches of --global-batch samples (effective batch = global batch x K; one '
+                        'gradient sync and one update per K backward passes; works inside --graph)')
     return p
+
+
+def _accum_steps(v):
+    k = int(v)
+    if k < 1:
+        raise argparse.ArgumentTypeError("--accum-steps must be >= 1")
+    return k
 
 
 def optimizer_from_args(args, params, lr):
@@ -106,13 +117,17 @@ def optimizer_from_args(args, params, lr):
 def lr_schedule_from_args(args, steps_per_epoch):
     """(base lr, LRSchedule | None) of a run: the linear scaling rule applied to --lr, and a
     schedule over epochs x steps_per_epoch steps (the partial last batch of an epoch is a step)
-    only when --lr-schedule or --warmup-steps asks for one."""
+    only when --lr-schedule or --warmup-steps asks for one. ``steps_per_epoch`` counts loader
+    batches; with --accum-steps K the effective batch is global batch x K and an epoch has
+    ceil(steps_per_epoch / K) optimizer steps (the leftover micro-batches form one)."""
     lr = float(args.lr)
+    accum = int(getattr(args, "accum_steps", 1) or 1)
     if args.lr_ref_batch:
-        lr *= args.global_batch / float(args.lr_ref_batch)
+        lr *= args.global_batch * accum / float(args.lr_ref_batch)
     if args.lr_schedule is None and not args.warmup_steps:
         return lr, None
     from ..optim.schedule import LRSchedule
+    steps_per_epoch = -(-int(steps_per_epoch) // accum)
     total = max(1, int(args.epochs) * int(steps_per_epoch))
     return lr, LRSchedule(lr, total, warmup_steps=min(int(args.warmup_steps), total),
                           decay=args.lr_schedule or "constant", milestones=args.lr_milestones,
