@@ -10,14 +10,13 @@ replay it. Host cost per step becomes one graph launch.
 Capture protocol: a few eager warm-up steps on a side stream (lazy allocations, autograd
 structures), then ``torch.cuda.graph`` capture; replays are bit-identical to eager steps.
 """
-import contextlib
 import os
 
 import torch
 
 from ..parallel.comm import is_live
 from ..utils.trace import trace_range
-from .trainer import micro_batch_ctx
+from .trainer import grad_scaled, micro_batch_ctx
 
 
 def capture_mode():
@@ -56,17 +55,12 @@ def sgd_in_backward_ok(model):
     return comm is None or not is_live(comm)
 
 
-def accum_grad_scale(grad_scale, m):
-    """Gradient scale of the update that consumes the sum of ``m`` micro-batch gradients:
-    float32(grad_scale / m), rounded on the host — the value every update site multiplies the
-    accumulated gradient by (exact for m a power of two)."""
-    if m == 1:
-        return grad_scale
-    return float(torch.tensor(float(grad_scale) / m, dtype=torch.float32))
-
-
 class TrainStep:
-    """``accum_steps`` = K > 1 (gradient accumulation): one step consumes K consecutive loader
+    """One training step, written once: ``_run`` makes m micro-batches (``_micro``) end in one
+    update. ``_body`` is ``_run`` over the loader's next K batches (eager, warm-up, and what
+    ``capture`` records for ``step`` to replay); ``tail_step`` is ``_run`` over explicit batches.
+
+    ``accum_steps`` = K > 1 (gradient accumulation): one step consumes K consecutive loader
     batches. Micro-steps 0..K-2 are batch launch (cursor offset j) + forward + backward into
     the gradient arena, which every producer adds to; the last micro-step is the plain step on
     batch cursor + K-1 with the update scaled by float32(grad_scale / K) and the cursor advanced
@@ -107,59 +101,69 @@ class TrainStep:
             raise ValueError("accum_steps > 1 needs the fused optimizer and the device loader "
                              "(the update launch scales, clears and advances the cursor)")
 
-    @contextlib.contextmanager
-    def _scaled(self, m):
-        """The optimizer's grad_scale set to float32(grad_scale / m) for the launches issued
-        inside (a launch argument: baked into a capture)."""
-        if m == 1:
-            yield
-            return
-        opt = self.optimizer
-        base = opt.grad_scale_factor
-        opt.grad_scale_factor = accum_grad_scale(base, m)
-        try:
-            yield
-        finally:
-            opt.grad_scale_factor = base
+    def _micro(self, j, last, m=1, batch=None, forward_loss=None):
+        """Micro-batch j of a step: batch, forward, backward into the gradient arena, and when
+        it is the step's ``last`` of ``m`` the gradient sync and the ONE update, scaled by
+        float32(grad_scale / m). ``batch`` = None: the loader's batch cursor + j, written into
+        its static buffers; the update launch then advances the cursor by m and stages the
+        schedule's next step. ``batch`` = (x, y), explicit: it does neither.
+        ``forward_loss``: a fused forward + loss to use in place of the model's own."""
+        fwd = forward_loss or (self.model.forward_loss if self.fused else None)
+        with micro_batch_ctx(self.model, j == 0, last), \
+                grad_scaled(self.optimizer, m if last else 1):
+            with trace_range("data"):
+                x, y = batch if batch is not None else self.loader.fill(
+                    advance=not self.fold_opt, offset=j, **(self._lr_sched() if j == 0 else {}))
+            with trace_range("forward"):
+                if fwd is not None:
+                    # classifier + loss + loss meter in one kernel (no logits tensor, no extra adds)
+                    loss = fwd(x, y, acc=self.loss_sum,
+                               **({"transient": True} if batch is None else {}))
+                else:
+                    loss = self.criterion(self.model(x), y)
+            with trace_range("backward"):
+                loss.backward(self._one)  # persistent ones: no fill kernel for the seed gradient
+            if last:
+                if self.sync is not None:
+                    with trace_range("sync"):
+                        self.sync(self.model)
+                with trace_range("optimizer"):
+                    if self.fold_opt:
+                        # the optimizer launch also clears the gradients for the next step and
+                        # advances the data cursor: no zero_grad fill, no counter kernel
+                        end = {"counter": self.loader.cursor_advance(m)} if batch is None else {}
+                        if end and self._lr_sched():
+                            end["lr_advance"] = "stage"
+                        self.optimizer.step(zero_grad=True,
+                                            fused_taken=self.opt_in_bwd and m == 1, **end)
+                    else:
+                        self.optimizer.step()
+        if fwd is None:
+            self.loss_sum.add_(loss.detach())
 
     def _accumulate(self, j):
         """Micro-step j < K-1: batch cursor + j, forward, backward; no sync, no update."""
-        with micro_batch_ctx(self.model, j == 0, False):
-            with trace_range("data"):
-                x, y = self.loader.fill(advance=False, offset=j,
-                                        **(self._lr_sched() if j == 0 else {}))
-            with trace_range("forward"):
-                if self.fused:
-                    loss = self.model.forward_loss(x, y, acc=self.loss_sum, transient=True)
-                else:
-                    loss = self.criterion(self.model(x), y)
-            with trace_range("backward"):
-                loss.backward(self._one)
-        if not self.fused:
-            self.loss_sum.add_(loss.detach())
+        self._micro(j, False)
 
-    def _body_accum(self):
-        K = self.accum_steps
-        for j in range(K - 1):
-            self._accumulate(j)
-        with self._scaled(K), micro_batch_ctx(self.model, False, True):
-            with trace_range("data"):
-                x, y = self.loader.fill(advance=False, offset=K - 1)
-            with trace_range("forward"):
-                if self.fused:
-                    loss = self.model.forward_loss(x, y, acc=self.loss_sum, transient=True)
-                else:
-                    loss = self.criterion(self.model(x), y)
-            with trace_range("backward"):
-                loss.backward(self._one)
-            if self.sync is not None:
-                with trace_range("sync"):
-                    self.sync(self.model)
-            with trace_range("optimizer"):
-                self.optimizer.step(zero_grad=True, counter=self.loader.cursor_advance(K),
-                                    **({"lr_advance": "stage"} if self._lr_sched() else {}))
-        if not self.fused:
-            self.loss_sum.add_(loss.detach())
+    def _run(self, m, batches=None):
+        """One optimizer step over m micro-batches, every execution form: the loader's batches
+        cursor .. cursor + m-1 (``_body``: eager, warm-up and what ``capture`` records), or the
+        explicit ``batches`` (``tail_step``). SGD in the backward only with m == 1."""
+        if m > 1 and not self.fold_opt:
+            raise ValueError("an accumulated step needs the fused optimizer and the device loader")
+        if batches is not None and self._lr_sched():
+            # no batch launch of the loader precedes this step: make the learning-rate step
+            # that the last replay staged current before the backward reads it
+            self.optimizer.commit_lr_step()
+        if not self.fold_opt:
+            self.optimizer.zero_grad()
+        in_bwd = self.opt_in_bwd and m == 1
+        if in_bwd:
+            self.optimizer.register_in_backward()
+        for j in range(m):
+            self._micro(j, j == m - 1, m, batches[j] if batches is not None else None)
+        if in_bwd:
+            self.optimizer.unregister_in_backward()
 
     def _fused_loss(self):
         """Use the model's fused classifier+loss when the criterion is the plain mean CE."""
@@ -169,38 +173,7 @@ class TrainStep:
                 and type(self.criterion) is CrossEntropyLoss)
 
     def _body(self):
-        if self.accum_steps > 1:
-            return self._body_accum()
-        if not self.fold_opt:
-            self.optimizer.zero_grad()
-        if self.opt_in_bwd:
-            self.optimizer.register_in_backward()
-        with trace_range("data"):
-            x, y = self.loader.fill(advance=not self.fold_opt, **self._lr_sched())
-        with trace_range("forward"):
-            if self.fused:
-                # classifier + loss + loss meter in one kernel (no logits tensor, no extra adds)
-                loss = self.model.forward_loss(x, y, acc=self.loss_sum, transient=True)
-            else:
-                loss = self.criterion(self.model(x), y)
-        with trace_range("backward"):
-            loss.backward(self._one)  # persistent ones: no fill kernel for the seed gradient
-        if self.sync is not None:
-            with trace_range("sync"):
-                self.sync(self.model)
-        with trace_range("optimizer"):
-            if self.fold_opt:
-                # the optimizer launch also clears the gradients for the next step and advances
-                # the data cursor: no zero_grad fill, no counter kernel
-                self.optimizer.step(zero_grad=True, counter=self.loader.cursor_advance(),
-                                    fused_taken=self.opt_in_bwd,
-                                    **({"lr_advance": "stage"} if self._lr_sched() else {}))
-            else:
-                self.optimizer.step()
-        if self.opt_in_bwd:
-            self.optimizer.unregister_in_backward()
-        if not self.fused:
-            self.loss_sum.add_(loss.detach())
+        self._run(self.accum_steps)
 
     def _lr_sched(self):
         """An attached learning-rate schedule advances without a dispatch of its own: the
@@ -252,56 +225,8 @@ class TrainStep:
         ``tail_step([(x0, y0), (x1, y1), ...])``: the m micro-batches left over at the end of
         an accumulated epoch as ONE optimizer step scaled by 1/m (each loss is the mean over
         its own samples)."""
-        if y is None:
-            batches = list(x)
-            if len(batches) > 1:
-                return self._tail_accum(batches)
-            x, y = batches[0]
-        if self._lr_sched():
-            # no batch launch of the loader precedes this step: make the learning-rate step
-            # that the last replay staged current before the backward reads it
-            self.optimizer.commit_lr_step()
-        if not self.fold_opt:
-            self.optimizer.zero_grad()
-        if self.opt_in_bwd:
-            self.optimizer.register_in_backward()
-        if self.fused:
-            loss = self.model.forward_loss(x, y, acc=self.loss_sum)
-        else:
-            loss = self.criterion(self.model(x), y)
-            self.loss_sum.add_(loss.detach())
-        loss.backward(self._one)
-        if self.sync is not None:
-            self.sync(self.model)
-        if self.fold_opt:
-            self.optimizer.step(zero_grad=True, fused_taken=self.opt_in_bwd)
-        else:
-            self.optimizer.step()
-        if self.opt_in_bwd:
-            self.optimizer.unregister_in_backward()
-
-    def _tail_accum(self, batches):
-        m = len(batches)
-        if not self.fold_opt:
-            raise ValueError("an accumulated step needs the fused optimizer and the device loader")
-        if self._lr_sched():
-            self.optimizer.commit_lr_step()
-        for j, (x, y) in enumerate(batches):
-            last = j == m - 1
-            with contextlib.ExitStack() as st:
-                st.enter_context(micro_batch_ctx(self.model, j == 0, last))
-                if last:
-                    st.enter_context(self._scaled(m))
-                if self.fused:
-                    loss = self.model.forward_loss(x, y, acc=self.loss_sum)
-                else:
-                    loss = self.criterion(self.model(x), y)
-                    self.loss_sum.add_(loss.detach())
-                loss.backward(self._one)
-                if last:
-                    if self.sync is not None:
-                        self.sync(self.model)
-                    self.optimizer.step(zero_grad=True)
+        batches = [(x, y)] if y is not None else list(x)
+        self._run(len(batches), batches)
 
     def wait(self, timeout_s=None, poll_s=0.001):
         """Synchronise with the device, optionally bounded: returns False on timeout instead of
@@ -526,10 +451,6 @@ class SegmentedDDPStep(TrainStep):
         torch.cuda.current_stream().wait_stream(self.comm_stream)
         super().tail_step(x, y)
 
-    def _advance(self):
-        """The step's pending cursor increment: its K micro-batches."""
-        return self.loader.cursor_advance(self.accum_steps)
-
     def _probe_event(self, stream):
         ev = torch.cuda.Event(enable_timing=True)
         ev.record(stream)
@@ -569,13 +490,7 @@ class SegmentedDDPStep(TrainStep):
         K = self.accum_steps
         with self.ddp.no_sync():
             for j in range(K - 1):  # accumulate-only micro-steps: whole, uncut, no collective
-                with trace_range("data"):
-                    x, y = self.loader.fill(advance=False, offset=j,
-                                            **(self._lr_sched() if j == 0 else {}))
-                with trace_range("forward"):
-                    loss = self.ddp.module.forward_loss(x, y, acc=self.loss_sum, transient=True)
-                with trace_range("backward"):
-                    loss.backward(self._one)
+                self._micro(j, False, forward_loss=self.ddp.module.forward_loss)
             with trace_range("data"):
                 x, y = self.loader.fill(advance=False, offset=K - 1,
                                         **(self._lr_sched() if K == 1 else {}))
@@ -608,7 +523,7 @@ class SegmentedDDPStep(TrainStep):
         (i0, i1), (lo, hi) = self.buckets[j]
         last = j == len(self.buckets) - 1
         t0 = self._probe_event(cs) if self.probe is not None else None
-        with self._scaled(self.accum_steps):
+        with grad_scaled(self.optimizer, self.accum_steps):
             self._comm_body(j, cs, i0, i1, lo, hi, last)
         if t0 is not None:
             self.probe.append((j, t0, self._probe_event(cs)))
@@ -638,22 +553,24 @@ class SegmentedDDPStep(TrainStep):
 
     def _comm_body(self, j, cs, i0, i1, lo, hi, last):
         from ..ops.common import native
+        # what the launch that ends the step carries: the cursor advance over the step's K
+        # micro-batches and the staging of the schedule's next step; the all-reduce plans' last
+        # update also signals D
+        end = {"skip": self._fp(4),
+               "counter": self.loader.cursor_advance(self.accum_steps) if last else None,
+               "lr_advance": "stage" if last else False}
+        signal = {"signal": (self._fp(5), self._fp(1))} if last else {}
         if self.shard16 is not None:
             if self.update[j] == "s16":
                 self._standin_bucket = j
                 with trace_range(f"shard16_update_bucket{j}"):
-                    self.shard16.step(j, stream=cs, skip=self._fp(4),
-                                      counter=self._advance() if last else None,
-                                      lr_advance="stage" if last else False,
+                    self.shard16.step(j, stream=cs, **end,
                                       standin=self._standin(cs) if self.comm_a is None else None)
             else:
                 with trace_range(f"sync_bucket{j}"):
                     self._allreduce(lo, hi, cs, self.comm_a)
                 with trace_range(f"optimizer_bucket{j}"):
-                    self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs,
-                                        skip=self._fp(4),
-                                        counter=self._advance() if last else None,
-                                        lr_advance="stage" if last else False)
+                    self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs, **end)
             if last:  # small-tensor unpack + operand re-pack + signal D, one launch
                 with trace_range("shard16_tail"):
                     self.shard16.tail(stream=cs, done=self._fp(5), signal=self._fp(1),
@@ -661,9 +578,7 @@ class SegmentedDDPStep(TrainStep):
             return
         if self.zero is not None:
             with trace_range(f"zero_update_bucket{j}"):
-                self.zero.step(j, stream=cs, skip=self._fp(4),
-                               counter=self._advance() if last else None,
-                               lr_advance="stage" if last else False)
+                self.zero.step(j, stream=cs, **end)
             if last:
                 native().flag_signal(self._fp(1), cs.cuda_stream)
             return
@@ -678,9 +593,7 @@ class SegmentedDDPStep(TrainStep):
                 self.optimizer.grad_sumsq(params=(i0, i1), stream=cs)
             if last:
                 with trace_range("optimizer"):
-                    self.optimizer.step(zero_grad=True, stream=cs, skip=self._fp(4),
-                                        counter=self._advance(),
-                                        signal=(self._fp(5), self._fp(1)), lr_advance="stage",
+                    self.optimizer.step(zero_grad=True, stream=cs, **end, **signal,
                                         norm_done=True)
             return
         with trace_range(f"optimizer_bucket{j}"):
@@ -690,10 +603,7 @@ class SegmentedDDPStep(TrainStep):
             # flags[5]): no separate signal launch on the critical comm stream. It also stages
             # the next step of an attached learning-rate schedule (lr_advance; the next step's
             # batch launch, which waits for D, makes it current)
-            self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs, skip=self._fp(4),
-                                counter=self._advance() if last else None,
-                                signal=(self._fp(5), self._fp(1)) if last else None,
-                                lr_advance="stage" if last else False)
+            self.optimizer.step(zero_grad=True, params=(i0, i1), stream=cs, **end, **signal)
 
     def _segments(self):
         return [self._seg_first] + [(lambda j=j: self._seg(j)) for j in range(1, len(self.buckets))]

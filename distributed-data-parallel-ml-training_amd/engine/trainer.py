@@ -70,119 +70,102 @@ def _groups(loader, k):
         yield group
 
 
-def _train_model_accum(model, train_loader, optimizer, criterion, epoch, device, sync, log,
-                       metrics, watchdog, rank, accum_steps):
-    """``train_model`` with gradient accumulation: an iteration is one optimizer step over up
-    to ``accum_steps`` consecutive batches (the epoch's last group may hold fewer, m), each
-    the gradient sync (DDP buckets, 2A/2B) once, after the last micro-batch. Where the 1/m goes:
+@contextlib.contextmanager
+def grad_scaled(optimizer, m):
+    """The optimizer's grad_scale set, for the launches issued inside (a launch argument: baked
+    into a capture), to that of the update that consumes the sum of ``m`` micro-batch
+    gradients: float32(grad_scale / m), rounded on the host — the value every update site
+    multiplies the accumulated gradient by (exact for m a power of two). m == 1 touches
+    nothing."""
+    if m == 1:
+        yield
+        return
+    base = optimizer.grad_scale_factor
+    optimizer.grad_scale_factor = float(torch.tensor(float(base) / m, dtype=torch.float32))
+    try:
+        yield
+    finally:
+        optimizer.grad_scale_factor = base
+
+
+class _Iterations:
+    """Per-iteration bookkeeping of both loops (an iteration is one optimizer step): the timer,
+    the ``[epoch, batch] loss`` line every 20 iterations, the 1..39 window and its two prints,
+    the metrics record (``accum`` only with accumulation), the watchdog beat, ``stats``."""
+
+    def __init__(self, optimizer, epoch, rank, log, metrics, watchdog, accum_steps):
+        self.optimizer, self.epoch, self.rank, self.log = optimizer, epoch, rank, log
+        self.metrics, self.watchdog, self.accum = metrics, watchdog, accum_steps > 1
+        self.stats = {"iter_ns": [], "total_1_39_ns": 0}
+
+    def begin(self, it):
+        fault_point(self.rank, it)
+        self.start = time.perf_counter_ns()
+        self.lr = _scheduled_lr(self.optimizer)
+
+    def end(self, it, m, mean_loss):
+        """``mean_loss()``: the value of the loss line, asked for when one is due; returns
+        whether it was (the caller then starts its running mean anew)."""
+        due = it % 20 == 19
+        if due:
+            self.log(f'[{self.epoch + 1}, {it + 1:5d}] loss: {mean_loss():.3f}')
+        dt = time.perf_counter_ns() - self.start
+        st = self.stats
+        st["iter_ns"].append(dt)
+        if 0 < it < 40:
+            st["total_1_39_ns"] += dt
+        if it == 39:
+            self.log(f'Total time for 1-39 iteration in ns: {st["total_1_39_ns"]}')
+            self.log(f'Average time for 1-39 iteration in ns: {st["total_1_39_ns"] / 39.0}')
+        if self.metrics is not None:
+            self.metrics.log(event="iter", epoch=self.epoch, batch=it, ns=dt,
+                             **({"accum": m} if self.accum else {}), **self.lr,
+                             **_guard_stats(self.optimizer))
+        if self.watchdog is not None:
+            self.watchdog.beat()
+        return due
+
+
+def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", sync=None,
+                log=print, metrics=None, watchdog=None, rank=0, accum_steps=1):
+    """An iteration is one optimizer step over up to ``accum_steps`` consecutive batches (1: the
+    reference's loop; the epoch's last group may hold fewer, m), with the gradient sync (DDP
+    buckets, 2A/2B) once, after the last micro-batch. Where the 1/m goes:
     the fused optimizer of the GPU takes it as float32(grad_scale / m) in its update launch, as
     the captured steps do (the micro-batch gradients are the plain ones: scaling the loss would
     round every bf16 activation gradient differently when m is no power of two); every other
     optimizer path (torch.optim.SGD on the CPU ignores grad_scale) gets each backward on
-    loss / m."""
+    loss / m. The losses are read after the step (the reference's order: one host
+    synchronisation per iteration)."""
     fused = bool(getattr(optimizer, "_fused", False)) and hasattr(optimizer, "grad_scale_factor")
+    book = _Iterations(optimizer, epoch, rank, log, metrics, watchdog, accum_steps)
     running_loss = 0.0
-    total_time = 0
-    stats = {"iter_ns": []}
     for it, group in enumerate(_groups(train_loader, accum_steps)):
-        fault_point(rank, it)
-        start_time = time.perf_counter_ns()
-        lr = _scheduled_lr(optimizer)
+        book.begin(it)
         m = len(group)
-        optimizer.zero_grad()
-        loss_sum = 0.0
+        losses = []
         for j, (data, target) in enumerate(group):
             with trace_range("data"):
                 data, target = data.to(device), target.to(device)
+            if j == 0:
+                optimizer.zero_grad()
             with micro_batch_ctx(model, j == 0, j == m - 1):
                 with trace_range("forward"):
                     output = model(data)
                     loss = criterion(output, target)
                 with trace_range("backward"):
-                    (loss if fused else loss / m).backward()
-            loss_sum += loss.item()
+                    (loss if fused or m == 1 else loss / m).backward()
+            losses.append(loss.detach())
         if sync is not None:
             with trace_range("sync"):
                 sync(model)
-        with trace_range("optimizer"):
-            if fused and m > 1:
-                base = optimizer.grad_scale_factor
-                optimizer.grad_scale_factor = float(torch.tensor(float(base) / m,
-                                                                 dtype=torch.float32))
-                try:
-                    optimizer.step()
-                finally:
-                    optimizer.grad_scale_factor = base
-            else:
-                optimizer.step()
-
-        running_loss += loss_sum / m
-        if it % 20 == 19:
-            log(f'[{epoch + 1}, {it + 1:5d}] loss: {running_loss / 20:.3f}')
-            running_loss = 0.0
-
-        dt = time.perf_counter_ns() - start_time
-        stats["iter_ns"].append(dt)
-        if 0 < it < 40:
-            total_time += dt
-        if it == 39:
-            log(f'Total time for 1-39 iteration in ns: {total_time}')
-            log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
-        if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=it, ns=dt, accum=m, **lr,
-                        **_guard_stats(optimizer))
-        if watchdog is not None:
-            watchdog.beat()
-    stats["total_1_39_ns"] = total_time
-    return stats
-
-
-def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", sync=None,
-                log=print, metrics=None, watchdog=None, rank=0, accum_steps=1):
-    if accum_steps > 1:
-        return _train_model_accum(model, train_loader, optimizer, criterion, epoch, device,
-                                  sync, log, metrics, watchdog, rank, accum_steps)
-    running_loss = 0.0
-    total_time = 0
-    stats = {"iter_ns": []}
-    for batch_idx, (data, target) in enumerate(train_loader):
-        fault_point(rank, batch_idx)
-        start_time = time.perf_counter_ns()
-        lr = _scheduled_lr(optimizer)
-        with trace_range("data"):
-            data, target = data.to(device), target.to(device)
-
-        optimizer.zero_grad()
-        with trace_range("forward"):
-            output = model(data)
-            loss = criterion(output, target)
-        with trace_range("backward"):
-            loss.backward()
-        if sync is not None:
-            with trace_range("sync"):
-                sync(model)
-        with trace_range("optimizer"):
+        with trace_range("optimizer"), grad_scaled(optimizer, m if fused else 1):
             optimizer.step()
 
-        running_loss += loss.item()
-        if batch_idx % 20 == 19:
-            log(f'[{epoch + 1}, {batch_idx + 1:5d}] loss: {running_loss / 20:.3f}')
+        running_loss += sum(v.item() for v in losses) / m
+        if book.end(it, m, lambda: running_loss / 20):
             running_loss = 0.0
-
-        dt = time.perf_counter_ns() - start_time
-        stats["iter_ns"].append(dt)
-        if 0 < batch_idx < 40:
-            total_time += dt
-        if batch_idx == 39:
-            log(f'Total time for 1-39 iteration in ns: {total_time}')
-            log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
-        if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr,
-                        **_guard_stats(optimizer))
-        if watchdog is not None:
-            watchdog.beat()
-    stats["total_1_39_ns"] = total_time
-    return stats
+    return book.stats
 
 
 def train_model_graph(step, train_loader, epoch, log=print, metrics=None, watchdog=None, rank=0,
@@ -200,91 +183,35 @@ def train_model_graph(step, train_loader, epoch, log=print, metrics=None, watchd
 
     ``accum_steps`` = K > 1 (the step was built with the same K): an iteration is one optimizer
     step — a replay over K batches, or at the end of the epoch ONE eager step over the leftover
-    full batches and the partial batch (``accum_epoch_plan``)."""
-    if accum_steps > 1:
-        return _train_model_graph_accum(step, train_loader, epoch, log, metrics, watchdog, rank,
-                                        accum_steps)
-    total_time = 0
-    stats = {"iter_ns": []}
-    nb = len(train_loader)
-    L, B = train_loader.idx.numel(), train_loader.batch_size
-    nfull = L // B
-    step.pop_loss()
-    for batch_idx in range(nb):
-        fault_point(rank, batch_idx)
-        start_time = time.perf_counter_ns()
-        lr = _scheduled_lr(step.optimizer)
-        if batch_idx < nfull:
-            step.step()
-        else:
-            step.tail_step(*train_loader.batch(batch_idx * B, L - batch_idx * B))
-        torch.cuda.synchronize()
-        if batch_idx % 20 == 19:
-            log(f'[{epoch + 1}, {batch_idx + 1:5d}] loss: {step.pop_loss() / 20:.3f}')
-        dt = time.perf_counter_ns() - start_time
-        stats["iter_ns"].append(dt)
-        if 0 < batch_idx < 40:
-            total_time += dt
-        if batch_idx == 39:
-            log(f'Total time for 1-39 iteration in ns: {total_time}')
-            log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
-        if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=batch_idx, ns=dt, **lr,
-                        **_guard_stats(step.optimizer))
-        if watchdog is not None:
-            watchdog.beat()
-    if hasattr(step, "check_error"):
-        step.check_error()
-    stats["total_1_39_ns"] = total_time
-    stats["graph_replays"] = min(nb, nfull)
-    return stats
-
-
-def _train_model_graph_accum(step, train_loader, epoch, log, metrics, watchdog, rank, K):
+    full batches and the partial batch (``accum_epoch_plan``; with K = 1 that is
+    ``graph_epoch_plan``: the partial batch alone)."""
+    K = accum_steps
     if getattr(step, "accum_steps", 1) != K:
         raise ValueError(f"the step accumulates {getattr(step, 'accum_steps', 1)} micro-batches, "
                          f"the loop was asked for {K}")
-    total_time = 0
-    stats = {"iter_ns": []}
+    book = _Iterations(step.optimizer, epoch, rank, log, metrics, watchdog, K)
     L, B = train_loader.idx.numel(), train_loader.batch_size
     replays, left, tail = accum_epoch_plan(L, B, K, train_loader.max_batches)
-    n_iter = replays + (1 if left or tail else 0)
+    sizes = [B] * left + ([tail] if tail else [])  # the epoch's last, eager step
     step.pop_loss()
     micro = 0  # micro-batches in the loss meter since the last print
-    for it in range(n_iter):
-        fault_point(rank, it)
-        start_time = time.perf_counter_ns()
-        lr = _scheduled_lr(step.optimizer)
+    for it in range(replays + (1 if sizes else 0)):
+        book.begin(it)
         if it < replays:
             step.step()
             m = K
         else:
-            first = replays * K
-            sizes = [B] * left + ([tail] if tail else [])
             m = len(sizes)
-            step.tail_step([train_loader.batch((first + j) * B, n) for j, n in enumerate(sizes)])
+            step.tail_step([train_loader.batch((replays * K + j) * B, n)
+                            for j, n in enumerate(sizes)])
         micro += m
         torch.cuda.synchronize()
-        if it % 20 == 19:
-            log(f'[{epoch + 1}, {it + 1:5d}] loss: {step.pop_loss() / micro:.3f}')
+        if book.end(it, m, lambda: step.pop_loss() / micro):
             micro = 0
-        dt = time.perf_counter_ns() - start_time
-        stats["iter_ns"].append(dt)
-        if 0 < it < 40:
-            total_time += dt
-        if it == 39:
-            log(f'Total time for 1-39 iteration in ns: {total_time}')
-            log(f'Average time for 1-39 iteration in ns: {total_time / 39.0}')
-        if metrics is not None:
-            metrics.log(event="iter", epoch=epoch, batch=it, ns=dt, accum=m, **lr,
-                        **_guard_stats(step.optimizer))
-        if watchdog is not None:
-            watchdog.beat()
     if hasattr(step, "check_error"):
         step.check_error()
-    stats["total_1_39_ns"] = total_time
-    stats["graph_replays"] = replays
-    return stats
+    book.stats["graph_replays"] = replays
+    return book.stats
 
 
 def accum_epoch_plan(n_samples, batch, K, max_batches=None):

@@ -44,7 +44,6 @@ _SHARDED = ("LARS needs every tensor's whole gradient for its norm: the sharded 
 
 class LARS(FusedSGD):
     needs_whole_tensors = True
-    CHUNK = 8192  # elements per norm block (optim.hip kNormChunk; the SGD items' chunking)
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, grad_scale=1.0, trust_coefficient=0.001, eps=1e-8,
@@ -64,12 +63,9 @@ class LARS(FusedSGD):
         self._trust_cpu = None
         if self._fused:
             a, dev = self.arena, self.arena.data.device
-            self._chunk0, c = [], 0
-            for n in a.numels:
-                self._chunk0.append(c)
-                c += -(-n // self.CHUNK)
             # allocated once: captured launches keep these addresses
-            self._lars_partial = torch.zeros(max(c, 1), 2, dtype=torch.float32, device=dev)
+            self._lars_partial = torch.zeros(max(self._n_chunks, 1), 2, dtype=torch.float32,
+                                             device=dev)
             self._lars_trust = torch.ones(len(a.params), dtype=torch.float32, device=dev)
             self._lars_tensors = torch.zeros(len(a.params), 4, dtype=torch.int32, device=dev)
             self._adapted_for = None
@@ -213,22 +209,12 @@ class LARS(FusedSGD):
         if n_norm:
             native().lars_norms(nitems.data_ptr(), n_norm, a.data.data_ptr(), a.grad.data_ptr(),
                                 gs, self._lars_partial.data_ptr(), s)
-        native().sgd_pack(items.data_ptr(), n_items, descs.data_ptr(), a.data.data_ptr(),
-                          a.grad.data_ptr(), self.momentum_buffer.data_ptr(), float(g["lr"]),
-                          float(g["momentum"]), float(g["weight_decay"]), gs,
-                          int(bool(g["nesterov"])), s,
-                          zero_grad=int(bool(zero_grad)),
-                          counter=int(counter[0]) if counter else 0,
-                          delta=int(counter[1]) if counter else 0,
-                          skip=int(skip) if skip else 0,
-                          done=int(signal[0]) if signal else 0,
-                          signal=int(signal[1]) if signal else 0,
-                          lars_side=side.data_ptr(), lars_tensors=tensors.data_ptr(),
-                          lars_partial=self._lars_partial.data_ptr(),
-                          lars_trust=self._lars_trust.data_ptr(),
-                          lars_eta=float(g["trust_coefficient"]), lars_eps=float(g["eps"]),
-                          **self._sched_kw(lr_advance), **self._clip_kw(lr_advance))
-        self._sched_commit(lr_advance, s)
+        self._update_launch(items, n_items, s, descs=descs, zero_grad=zero_grad, counter=counter,
+                            skip=skip, signal=signal, lr_advance=lr_advance,
+                            lars_side=side.data_ptr(), lars_tensors=tensors.data_ptr(),
+                            lars_partial=self._lars_partial.data_ptr(),
+                            lars_trust=self._lars_trust.data_ptr(),
+                            lars_eta=float(g["trust_coefficient"]), lars_eps=float(g["eps"]))
         return None
 
     def load_state_dict(self, sd):

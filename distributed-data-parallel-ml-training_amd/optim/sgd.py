@@ -38,6 +38,8 @@ CPU the norm is taken in fp64 and rounded once to fp32 (the oracle of the kernel
 gradients are multiplied by gs * c in place and torch.optim.SGD does the rest (the unguarded
 CPU path is torch.optim.SGD as is and, as before, does not apply ``grad_scale``).
 """
+import itertools
+
 import torch
 
 from .arena import arena_for
@@ -69,6 +71,11 @@ class FusedSGD(torch.optim.SGD):
                 raise ValueError("fused SGD supports a single param group")
             self.arena = arena_for(params)
             self.momentum_buffer = torch.zeros_like(self.arena.data)
+            # first chunk of each parameter, numbered over the arena: the slots of the guard's
+            # and LARS' per-chunk partial sums
+            first = list(itertools.accumulate((-(-n // self.CHUNK) for n in self.arena.numels),
+                                              initial=0))
+            self._chunk0, self._n_chunks = first[:-1], first[-1]
         else:
             # CPU: plain torch.optim.SGD; the flat arena (if the DDP wrapper built one) serves the
             # element-range update of the ZeRO-1 path (step_elements)
@@ -120,13 +127,9 @@ class FusedSGD(torch.optim.SGD):
                 self.defaults.pop(k, None)
             self.__dict__.pop("needs_whole_tensors", None)
         if on and self._fused and self._guard_dev is None:
-            a, dev = self.arena, self.arena.data.device
-            self._chunk0, c = [], 0  # first chunk of each parameter, numbered over the arena
-            for n in a.numels:
-                self._chunk0.append(c)
-                c += -(-n // self.CHUNK)
-            self._n_chunks = c
-            self._sumsq_partial = torch.zeros(max(c, 1), dtype=torch.float32, device=dev)
+            dev = self.arena.data.device
+            self._sumsq_partial = torch.zeros(max(self._n_chunks, 1), dtype=torch.float32,
+                                              device=dev)
             self._guard_dev = torch.zeros(4, dtype=torch.float32, device=dev)
             self._guard_dev[1] = 1.0
             self._sumsq_tables = {}
@@ -496,20 +499,37 @@ class FusedSGD(torch.optim.SGD):
             if zero_grad:
                 gr.zero_()
             return
-        from ..ops.common import native, stream_handle
+        from ..ops.common import stream_handle
         s = stream.cuda_stream if stream is not None else stream_handle()
         items, n_items = self._elem_table(lo, hi)
-        native().sgd_pack(items.data_ptr(), n_items, self._descs_ptr(), a.data.data_ptr(),
-                          a.grad.data_ptr(), self.momentum_buffer.data_ptr(), lr, m, wd,
+        self._update_launch(items, n_items, s, zero_grad=zero_grad, counter=counter, skip=skip,
+                            lr_advance=lr_advance)
+
+    def _descs_ptr(self):
+        return self._work_table()[2].data_ptr()
+
+    def _update_launch(self, items, n_items, s, descs=None, zero_grad=False, counter=None,
+                       skip=None, signal=None, lr_advance=False, **native_kw):
+        """The one native update launch: ``n_items`` work items on the raw stream ``s`` with
+        this optimizer's hyper-parameters and ``grad_scale_factor``. Step-level options as in
+        ``step``; ``descs``: the table a ``_work_table`` call just returned (default: looked
+        up); ``native_kw``: further native keywords (LARS', the sharded update's ``shadow`` /
+        ``slot``). The schedule's and the guard's keywords go in only when they are on."""
+        from ..ops.common import native
+        g, a = self.param_groups[0], self.arena
+        native().sgd_pack(items.data_ptr(), n_items,
+                          descs.data_ptr() if descs is not None else self._descs_ptr(),
+                          a.data.data_ptr(), a.grad.data_ptr(), self.momentum_buffer.data_ptr(),
+                          float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]),
                           float(self._grad_scale_factor), int(bool(g["nesterov"])), s,
                           zero_grad=int(bool(zero_grad)),
                           counter=int(counter[0]) if counter else 0,
                           delta=int(counter[1]) if counter else 0,
-                          skip=int(skip) if skip else 0, **self._sched_kw(lr_advance))
+                          skip=int(skip) if skip else 0,
+                          done=int(signal[0]) if signal else 0,
+                          signal=int(signal[1]) if signal else 0, **native_kw,
+                          **self._sched_kw(lr_advance), **self._clip_kw(lr_advance))
         self._sched_commit(lr_advance, s)
-
-    def _descs_ptr(self):
-        return self._work_table()[2].data_ptr()
 
     def repack_params(self, i0, i1, stream=None):
         """Rebuild the bf16 operand copies of the conv weights among parameters [i0, i1)."""
@@ -570,9 +590,7 @@ class FusedSGD(torch.optim.SGD):
                 super().zero_grad(set_to_none=False)
             return out
         from ..ops.common import native, stream_handle
-        g = self.param_groups[0]
         s = stream.cuda_stream if stream is not None else stream_handle()
-        a = self.arena
         exclude = pack_only = frozenset()
         if fused_taken:
             if self.guarded:
@@ -595,18 +613,8 @@ class FusedSGD(torch.optim.SGD):
                 native().flag_signal(int(signal[1]), s)
             return None
         # one launch: SGD over every tensor + bf16 re-pack of every conv weight
-        native().sgd_pack(items.data_ptr(), n_items, descs.data_ptr(), a.data.data_ptr(),
-                          a.grad.data_ptr(), self.momentum_buffer.data_ptr(), float(g["lr"]),
-                          float(g["momentum"]), float(g["weight_decay"]),
-                          float(self._grad_scale_factor), int(bool(g["nesterov"])), s,
-                          zero_grad=int(bool(zero_grad)),
-                          counter=int(counter[0]) if counter else 0,
-                          delta=int(counter[1]) if counter else 0,
-                          skip=int(skip) if skip else 0,
-                          done=int(signal[0]) if signal else 0,
-                          signal=int(signal[1]) if signal else 0, **sched,
-                          **self._clip_kw(lr_advance))
-        self._sched_commit(lr_advance, s)
+        self._update_launch(items, n_items, s, descs=descs, zero_grad=zero_grad, counter=counter,
+                            skip=skip, signal=signal, lr_advance=lr_advance)
         return None
 
     def state_dict(self):

@@ -351,32 +351,23 @@ class ShardedBf16Update:
         ``lr_advance``: this bucket's update ends the training step (optim/sgd.py step)."""
         if not self.cuda:
             return self._step_cpu(j)
-        from ..ops.common import native, stream_handle
+        from ..ops.common import stream_handle
         from .comm import AVG
-        nat = native()
         (_, (lo, hi)) = self.buckets[j]
         plan = self._plan[j]
         s0, s1 = self.shard(j)
         per = s1 - s0
-        a, opt = self.arena, self.opt
-        g = opt.param_groups[0]
         cs = stream.cuda_stream if stream is not None else stream_handle()
         items, n_items = self._tables[j]
-        gp, dp, sp = a.grad.data_ptr(), a.data.data_ptr(), self.data16.data_ptr()
+        gp, sp = self.arena.grad.data_ptr(), self.data16.data_ptr()
         slot_row = self.slots.data_ptr() + 4 * (plan["slot_base"] + self.rank * plan["M"])
         slot_all = self.slots.data_ptr() + 4 * plan["slot_base"]
         if standin is not None:
             standin("reduce_scatter", 4 * (hi - lo), gp + 4 * lo, hi - lo)
         else:
             self.comm.comm.reduce_scatter(gp + 4 * lo, gp + 4 * s0, per, 0, AVG, cs)
-        nat.sgd_pack(items.data_ptr(), n_items, opt._descs_ptr(), dp, gp,
-                     opt.momentum_buffer.data_ptr(), float(g["lr"]), float(g["momentum"]),
-                     float(g["weight_decay"]), float(opt._grad_scale_factor),
-                     int(bool(g["nesterov"])), cs, zero_grad=1,
-                     counter=int(counter[0]) if counter else 0,
-                     delta=int(counter[1]) if counter else 0, skip=int(skip) if skip else 0,
-                     shadow=sp, slot=slot_row, **opt._sched_kw(lr_advance))
-        opt._sched_commit(lr_advance, cs)
+        self.opt._update_launch(items, n_items, cs, zero_grad=True, counter=counter, skip=skip,
+                                lr_advance=lr_advance, shadow=sp, slot=slot_row)
         if standin is not None:
             standin("all_gather", 2 * (hi - lo) + 4 * self.world * plan["M"], slot_all, 0)
         else:

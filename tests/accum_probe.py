@@ -9,6 +9,9 @@ VGG-11, batch 8, 64 samples; every comparison is torch.equal.
     python tests/accum_probe.py ddp     # pipelined step (all-reduce / sharded plan) == TrainStep
     python tests/accum_probe.py guard   # gradient clipping and LARS: eager == captured; the norm
     python tests/accum_probe.py tail    # the leftover step and the eager loop == made by hand
+    python tests/accum_probe.py loop1   # the captured K = 1 loop with a partial last batch == by hand
+    python tests/accum_probe.py digest  # a SHA-256 of the end state per configuration: run in two
+                                        #   checkouts, the outputs must be equal key for key
 """
 import copy
 import json
@@ -33,7 +36,7 @@ def _setup():
 class Rig:
     """One model + optimizer + loader with a start state every run returns to."""
 
-    def __init__(self, base, opt_cls=None, ddp=False, **opt_kw):
+    def __init__(self, base, opt_cls=None, ddp=False, n=N, **opt_kw):
         import torch
         from ddp_amd.data import DeviceLoader, SyntheticCIFAR10
         from ddp_amd.optim import FusedSGD
@@ -45,7 +48,7 @@ class Rig:
                 self.model, RcclCommunicator(0, 1, 0, self_comm=False), bucket_cap_mb=256.0,
                 first_bucket_cap_mb=256.0)
         self.opt = (opt_cls or FusedSGD)(self.model.parameters(), **dict(HP, **opt_kw))
-        self.ld = DeviceLoader(SyntheticCIFAR10(True, n=N), B, "cuda")
+        self.ld = DeviceLoader(SyntheticCIFAR10(True, n=n), B, "cuda")
         self.arena = self.opt.arena
         self.snap = (self.arena.data.clone(), self.opt.momentum_buffer.clone())
         torch.cuda.synchronize()
@@ -56,6 +59,8 @@ class Rig:
         self.opt.momentum_buffer.copy_(self.snap[1])
         self.ld.cursor.zero_()
         self.arena.grad.zero_()
+        if self.opt.schedule is not None:
+            self.opt.set_lr_step(0)
         for sp in self.inner.fused_plan():
             sp._packed_version = None
             sp.maybe_pack()
@@ -340,9 +345,168 @@ def tail_case():
     return res
 
 
+def _sched(opt):
+    """The cosine schedule of tests/test_gpu_accum.py."""
+    from ddp_amd.optim.schedule import LRSchedule
+    opt.set_schedule(LRSchedule(0.01, 64, warmup_steps=2, decay="cosine"))
+
+
+class Sink:
+    def __init__(self):
+        self.recs = []
+
+    def log(self, **kw):
+        self.recs.append(kw)
+
+    def timeless(self):
+        return [sorted((k, v) for k, v in r.items() if k != "ns") for r in self.recs]
+
+
+def loop1_case():
+    """train_model_graph with K = 1 over 60 samples at batch 8 (7 replays and an eager step on
+    the partial batch of 4) with the default TrainStep (SGD in the backward) and a schedule,
+    against the same eight steps made by hand."""
+    torch = _setup()
+    from ddp_amd.engine import CrossEntropyLoss, TrainStep
+    from ddp_amd.engine.trainer import train_model_graph
+    rig = Rig(_base(), n=60)
+    _sched(rig.opt)
+    st = TrainStep(rig.model, rig.opt, CrossEntropyLoss(), rig.ld)
+    res = {"opt_in_bwd": bool(st.opt_in_bwd), "batches": len(rig.ld) == 8}
+    st.warmup(2)
+    st.capture()
+    sink, stats = Sink(), {}
+    got = rig.run(lambda: stats.update(train_model_graph(st, rig.ld, 0, log=lambda s: None,
+                                                         metrics=sink)), steps=1)
+    res["grad_clear"] = float(rig.arena.grad.abs().max()) == 0.0
+    res["records"] = len(sink.recs) == 8 and [r["batch"] for r in sink.recs] == list(range(8))
+    res["no_accum_key"] = all("accum" not in r for r in sink.recs)
+    res["iters"] = len(stats["iter_ns"]) == 8
+    res["graph_replays"] = stats["graph_replays"] == 7
+    res["cursor"] = got["cursor"] == 7
+    res["lr_step"] = rig.opt.lr_step_device() == 8 and rig.opt.lr_step == 8
+    res["lr_values"] = [r["lr"] for r in sink.recs] == [rig.opt.schedule.lr_at(k)
+                                                        for k in range(8)]
+    res["moved"] = not torch.equal(got["p"], rig.snap[0])
+
+    def by_hand():
+        for _ in range(7):
+            st._body()
+        st.tail_step(*rig.ld.batch(56, 4))
+    res["equals_by_hand"] = same(got, rig.run(by_hand, steps=1))
+    res["by_hand_lr_step"] = rig.opt.lr_step_device() == 8 and rig.opt.lr_step == 8
+    return res
+
+
+def _digest(rig, fn, st=None, steps=2, extra=list):
+    """SHA-256 over masters, momentum, every operand copy, the cursor, the device's schedule
+    step and the raw bits of the popped loss meter after ``steps`` calls of ``fn`` from the
+    restored start state (``extra()``: further values, read afterwards, by their repr). The
+    digest of everything but the meter, and the meter's bits, also go to stderr: the head
+    kernel adds one partial loss per 4 rows to the meter with a float atomic, so from the second
+    micro-batch on the meter's last bit depends on which block of a batch of 8 adds first."""
+    import hashlib
+    import struct
+    import torch
+    rig.restore()
+    if st is not None:
+        st.pop_loss()
+    for _ in range(steps):
+        fn()
+    state = rig.state()
+    h = hashlib.sha256()
+    for t in [state["p"], state["buf"]] + state["ops"]:
+        h.update(t.contiguous().view(-1).view(torch.uint8).cpu().numpy().tobytes())
+    h.update(struct.pack("<qq", state["cursor"], rig.opt.lr_step_device()))
+    h.update(repr(extra()).encode())
+    meter = struct.pack("<f", st.pop_loss()) if st is not None else b""
+    print("state", h.hexdigest(), "meter", meter.hex(), file=sys.stderr)
+    h.update(meter)
+    return h.hexdigest()
+
+
+def digest_case():
+    """One digest per configuration; uses only names that the tree before the step routines
+    were unified has too, so the same file runs in both."""
+    _setup()
+    from ddp_amd.engine import CrossEntropyLoss, SegmentedDDPStep
+    from ddp_amd.engine.trainer import train_model, train_model_graph
+    from ddp_amd.optim import LARS
+    base = _base()
+    res = {}
+
+    def rig_of(**kw):
+        rig = Rig(base, **kw)
+        _sched(rig.opt)
+        return rig
+
+    def captured(name, rig, K, **kw):
+        st = _step(rig, K, **kw)
+        st.warmup(2)
+        st.capture()
+        res[name] = _digest(rig, st.step, st)
+        return st
+
+    st = captured("train/K1/in_bwd", rig_of(), 1)
+    assert st.opt_in_bwd
+    os.environ["DDP_AMD_SGD_IN_BWD"] = "0"
+    try:
+        st = captured("train/K1/no_in_bwd", rig_of(), 1)
+        assert not st.opt_in_bwd
+    finally:
+        del os.environ["DDP_AMD_SGD_IN_BWD"]
+    captured("train/K3", rig_of(), 3)
+    for K in (1, 2):
+        for upd in ("allreduce", "shard16"):
+            rig = rig_of(ddp=True)
+            st = _step(rig, K, cls=SegmentedDDPStep, split=[3, 6], emulate=1, update=upd)
+            st.WAIT_TIMEOUT_S = 20.0
+            st.warmup(2)
+            st.capture()
+            res[f"segmented/K{K}/{upd}"] = _digest(rig, st.step, st)
+            st.check_error()
+            rig.model.close()
+    captured("train/K2/clip", rig_of(max_grad_norm=1e-3), 2)
+    captured("train/K2/lars", rig_of(opt_cls=LARS, trust_coefficient=0.02), 2)
+
+    rig = rig_of()
+    st = _step(rig, 1)
+    st.warmup(2)
+    res["tail/partial4"] = _digest(rig, lambda: st.tail_step(*rig.ld.batch(0, 4)), st)
+    rig = rig_of()
+    st = _step(rig, 3)
+    st.warmup(1)
+    sizes = [(0, B), (B, B), (2 * B, 4)]
+    res["tail/list"] = _digest(
+        rig, lambda: st.tail_step([rig.ld.batch(s, n) for s, n in sizes]), st)
+
+    crit = CrossEntropyLoss()
+    for K in (1, 2):
+        rig = rig_of()
+        _step(rig, 1).warmup(1)  # builds the fused plan
+        rig.ld.max_batches = 3
+        sink = Sink()
+        res[f"eager_loop/K{K}"] = _digest(
+            rig, lambda: train_model(rig.model, rig.ld, rig.opt, crit, 0, "cuda",
+                                     log=lambda s: None, metrics=sink, accum_steps=K),
+            steps=1, extra=sink.timeless)
+    for K in (1, 3):
+        rig = rig_of(n=60)
+        st = _step(rig, K)
+        st.warmup(2)
+        st.capture()
+        sink = Sink()
+        res[f"graph_loop/K{K}"] = _digest(
+            rig, lambda: train_model_graph(st, rig.ld, 0, log=lambda s: None, metrics=sink,
+                                           accum_steps=K),
+            st, steps=1, extra=sink.timeless)
+    return res
+
+
 def main():
     res = {"sum": sum_case, "paths": paths_case, "k1": k1_case, "ddp": ddp_case,
-           "guard": guard_case, "tail": tail_case}[sys.argv[1]]()
+           "guard": guard_case, "tail": tail_case, "loop1": loop1_case,
+           "digest": digest_case}[sys.argv[1]]()
     print(json.dumps(res))
 
 

@@ -81,6 +81,18 @@ def test_accumulated_step_with_the_gradient_guard_and_lars(native_ext):
     _all_true(res)
 
 
+def test_captured_k1_loop_with_a_partial_last_batch(native_ext):
+    """train_model_graph with K = 1 over 60 samples at batch 8, the default TrainStep (SGD in
+    the backward) and the cosine schedule: 7 replays and one eager step on the partial batch of
+    4 leave, bit for bit, what seven ``_body()`` and one ``tail_step(*ld.batch(56, 4))`` leave;
+    8 metrics records without ``accum``, graph_replays 7, cursor 7, the schedule step 8 on the
+    device and in its host mirror, the records' ``lr`` the schedule's entries 0..7, and a
+    clear gradient arena."""
+    res = _probe("loop1")
+    assert res.pop("opt_in_bwd") is True
+    _all_true(res)
+
+
 def test_leftover_step_and_eager_loop_equal_the_hand_made_step(native_ext):
     """TrainStep.tail_step on a list of micro-batches (two full ones and a partial one: m = 3,
     a scale that is no power of two), the same list through SegmentedDDPStep.tail_step, and the
