@@ -86,6 +86,15 @@ static ddp_amd::ConvGeom geom(py::tuple g) {
   return c;
 }
 
+// conv weight pack descriptors from Python: (p, wc, wt, K, Cr, C, R, S, krsc) each
+using PackTuple = std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int, int, int, int, int>;
+static std::vector<ddp_amd::PackDesc> pack_descs(const std::vector<PackTuple>& descs) {
+  std::vector<ddp_amd::PackDesc> d;
+  for (const auto& [p, wc, wt, k, cr, c, r, s, krsc] : descs)
+    d.push_back({P<float>(p), P<unsigned short>(wc), P<unsigned short>(wt), k, cr, c, r, s, krsc});
+  return d;
+}
+
 PYBIND11_MODULE(_native, m) {
   m.doc() = "ddp_amd native extension: gfx950 HIP kernels + RCCL runtime";
 
@@ -532,20 +541,8 @@ PYBIND11_MODULE(_native, m) {
 #ifdef DDP_CONV_STAMPS
   m.def("conv_stamps_set", [](uintptr_t buf, int cap) { ddp_conv_stamps_set(P<void>(buf), cap); });
 #endif
-  // descs: list of (p, wc, wt, K, Cr, C, R, S, krsc)
-  m.def("pack_conv_weights", [](std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int,
-                                                       int, int, int, int>> descs, uintptr_t st) {
-    std::vector<ddp_amd::PackDesc> d;
-    for (auto& t : descs) {
-      ddp_amd::PackDesc x;
-      x.p = P<float>(std::get<0>(t));
-      x.wc = P<unsigned short>(std::get<1>(t));
-      x.wt = P<unsigned short>(std::get<2>(t));
-      x.K = std::get<3>(t); x.Cr = std::get<4>(t); x.C = std::get<5>(t);
-      x.R = std::get<6>(t); x.S = std::get<7>(t);
-      x.krsc = std::get<8>(t);
-      d.push_back(x);
-    }
+  m.def("pack_conv_weights", [](const std::vector<PackTuple>& descs, uintptr_t st) {
+    auto d = pack_descs(descs);
     check(ddp_pack_conv_weights(d.data(), (int)d.size(), S(st)), "pack_conv_weights");
   });
   m.def("sgd_pack", [](uintptr_t items, int n_items, uintptr_t descs, uintptr_t p, uintptr_t g,
@@ -557,15 +554,18 @@ PYBIND11_MODULE(_native, m) {
                        float lars_eta, float lars_eps, uintptr_t clip_partial, int clip_chunks,
                        float clip_max_norm, float clip_eps, int clip_flags,
                        uintptr_t clip_stats) {
-    check(ddp_sgd_pack(P<void>(items), n_items, P<long long>(descs), P<float>(p), P<float>(g),
-                       P<float>(buf), lr, momentum, wd, grad_scale, nesterov, zero_grad,
-                       P<int>(counter), delta, P<const unsigned>(skip), P<unsigned short>(shadow),
-                       P<float>(slot), P<unsigned>(done), P<unsigned>(signal),
-                       P<ddp_amd::LrSched>(sched), sched_advance, P<void>(lars_side),
-                       P<void>(lars_tensors), P<void>(lars_partial), P<float>(lars_trust),
-                       lars_eta, lars_eps, P<const float>(clip_partial), clip_chunks,
-                       clip_max_norm, clip_eps, clip_flags, P<float>(clip_stats), S(st)),
-          "sgd_pack");
+    ddp_amd::UpdateLaunch u{};
+    u.items = P<int4>(items); u.descs = P<ddp_amd::ConvDesc>(descs);
+    u.p = P<float>(p); u.g = P<float>(g); u.buf = P<float>(buf);
+    u.h = {lr, momentum, wd, grad_scale, nesterov, zero_grad, P<int>(counter), delta,
+           P<const unsigned>(skip), P<unsigned short>(shadow), P<float>(slot), P<unsigned>(done),
+           P<unsigned>(signal), P<ddp_amd::LrSched>(sched), sched_advance};
+    u.n_items = n_items;
+    u.lars = {P<int2>(lars_side), P<int4>(lars_tensors), P<float2>(lars_partial),
+              P<float>(lars_trust), lars_eta, lars_eps};
+    u.clip = {P<const float>(clip_partial), clip_chunks, clip_max_norm, clip_eps, clip_flags,
+              P<float>(clip_stats)};
+    check(ddp_sgd_pack(&u, S(st)), "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
      py::arg("nesterov"), py::arg("stream"), py::arg("zero_grad") = 0, py::arg("counter") = 0,
@@ -576,7 +576,7 @@ PYBIND11_MODULE(_native, m) {
      py::arg("lars_eps") = 0.f, py::arg("clip_partial") = 0, py::arg("clip_chunks") = 0,
      py::arg("clip_max_norm") = 0.f, py::arg("clip_eps") = 0.f, py::arg("clip_flags") = 0,
      py::arg("clip_stats") = 0);
-  // gradient guard (optim.hip grad_sumsq_kernel): per-chunk sum (g * grad_scale)^2 of every
+  // gradient guard (optim.hip chunk_sums_kernel<false>): per-chunk sum (g * grad_scale)^2 of every
   // parameter chunk in the items, the input of sgd_pack's clip_* arguments
   m.def("grad_sumsq", [](uintptr_t items, int n_items, uintptr_t g, float grad_scale,
                          uintptr_t partial, uintptr_t st) {
@@ -584,29 +584,18 @@ PYBIND11_MODULE(_native, m) {
                          S(st)), "grad_sumsq");
   }, py::arg("items"), py::arg("n_items"), py::arg("grad"), py::arg("grad_scale"),
      py::arg("partial"), py::arg("stream"));
-  // LARS norms launch (optim.hip lars_norms_kernel): per-chunk {sum p^2, sum (g * grad_scale)^2}
+  // LARS norms launch (optim.hip chunk_sums_kernel<true>): per-chunk {sum p^2,
+  // sum (g * grad_scale)^2}
   m.def("lars_norms", [](uintptr_t items, int n_items, uintptr_t p, uintptr_t g, float grad_scale,
                          uintptr_t partial, uintptr_t st) {
     check(ddp_lars_norms(P<void>(items), n_items, P<float>(p), P<float>(g), grad_scale,
                          P<void>(partial), S(st)), "lars_norms");
   }, py::arg("items"), py::arg("n_items"), py::arg("p"), py::arg("g"), py::arg("grad_scale"),
      py::arg("partial"), py::arg("stream"));
-  // descs: list of (p, wc, wt, K, Cr, C, R, S, krsc) as in pack_conv_weights
   m.def("shard_tail", [](uintptr_t segs, int n_segs, uintptr_t src, uintptr_t dst,
-                         std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int, int,
-                                                int, int, int>> descs,
-                         uintptr_t done, uintptr_t signal, uintptr_t skip, uintptr_t st) {
-    std::vector<ddp_amd::PackDesc> d;
-    for (auto& t : descs) {
-      ddp_amd::PackDesc x;
-      x.p = P<float>(std::get<0>(t));
-      x.wc = P<unsigned short>(std::get<1>(t));
-      x.wt = P<unsigned short>(std::get<2>(t));
-      x.K = std::get<3>(t); x.Cr = std::get<4>(t); x.C = std::get<5>(t);
-      x.R = std::get<6>(t); x.S = std::get<7>(t);
-      x.krsc = std::get<8>(t);
-      d.push_back(x);
-    }
+                         const std::vector<PackTuple>& descs, uintptr_t done, uintptr_t signal,
+                         uintptr_t skip, uintptr_t st) {
+    auto d = pack_descs(descs);
     check(ddp_shard_tail(P<void>(segs), n_segs, P<float>(src), P<float>(dst), d.data(),
                          (int)d.size(), P<unsigned>(done), P<unsigned>(signal),
                          P<const unsigned>(skip), S(st)), "shard_tail");

@@ -215,6 +215,80 @@ struct PackDesc {
   int krsc;
 };
 
+// Fused SGD + re-pack launch (optim.hip sgd_pack_kernel, optim/sgd.py FusedSGD._work_table).
+// One row of its conv descriptor table, 12 x int64 in device memory.
+struct ConvDesc {
+  long long p_offset;      // the fp32 master's first element in the arena
+  long long K, Cr, C, R, S;
+  unsigned short* wc;      // bf16 [K][R][S][C] (0: none)
+  unsigned short* wt;      // bf16 [C][R][S][K] (0: none)
+  long long krsc;          // master layout: [K][R][S][Cr] (1) or [K][Cr][R][S] (0)
+  long long pad[3];
+};
+static_assert(sizeof(ConvDesc) == 96 && offsetof(ConvDesc, wc) == 48 &&
+              offsetof(ConvDesc, krsc) == 64, "ConvDesc is the table's 12 x int64 row");
+
+struct SgdHyper {
+  float lr, momentum, wd, grad_scale;
+  int nesterov;
+  int zero_grad;  // write 0 to every gradient after use (replaces the next step's zero_grad fill)
+  int* counter;   // optional step counter (data cursor): += delta by one thread
+  int delta;
+  // optional error word (engine/step.py SegmentedDDPStep): non-zero when a device-side wait for
+  // a gradient bucket timed out — the update is then skipped instead of applying gradients
+  // that were never averaged (the host raises on the error at its next check)
+  const unsigned* skip;
+  // sharded update with a bf16 operand all-gather (parallel/zero.py ShardedBf16Update): item 3
+  // also stores bf16(new p) into ``shadow`` (the bf16 operand image of the arena, same element
+  // index) and, for the small fp32-wire tensors, the new p into ``slot`` (the all-gather send slot)
+  unsigned short* shadow;
+  float* slot;
+  // optional completion signal (engine/step.py SegmentedDDPStep, last bucket): the last block
+  // to finish (``done`` ticket, reset by it) release-increments ``signal`` — the step's
+  // "every parameter updated" flag without a separate signal launch
+  unsigned* done;
+  unsigned* signal;
+  // optional learning-rate schedule (LrSched): every block reads this step's rate from the
+  // table instead of ``lr``; ``sched_advance``: this launch ends the training step — block 0
+  // stages the next step (``next``, read by no block here; a later launch makes it current)
+  LrSched* sched;
+  int sched_advance;
+};
+
+// LARS (optim/lars.py): ``side`` non-null selects the LARS instantiations. ``partial`` is what
+// ddp_lars_norms wrote, launched before the update on the same stream.
+struct LarsArgs {
+  const int2* side;       // per work item: {parameter index | -1 (no ratio: item 5), first item}
+  const int4* tensors;    // per parameter: {first global chunk, chunks, adapted, -}
+  const float2* partial;  // per global chunk: {sum p^2, sum (g * grad_scale)^2}
+  float* trust;           // per parameter (written)
+  float eta, eps;
+};
+
+// Gradient guard (optim/sgd.py max_grad_norm / skip_nonfinite): ``partial`` non-null selects the
+// guarded instantiations — one float per 8192-element chunk of the WHOLE arena, sum
+// (g * grad_scale)^2 as written by ddp_grad_sumsq, launched before the update.
+struct ClipArgs {
+  const float* partial;
+  int n_chunks;          // chunks of the whole arena
+  float max_norm, eps;
+  int flags;             // 1: clip to max_norm, 2: skip a non-finite step, 4: this launch ends the
+                         // step (a skipped step is counted)
+  float* stats;          // 4 words {norm, coefficient, skipped steps (u32), -}, stored by block 0
+};
+
+struct UpdateLaunch {
+  const int4* items;      // work items, kinds 0-5 (optim.hip), one block each
+  int n_items;
+  const ConvDesc* descs;
+  float* p;               // the three arenas: masters, gradients, momentum
+  float* g;
+  float* buf;
+  SgdHyper h;
+  LarsArgs lars;          // optional: lars.side == null
+  ClipArgs clip;          // optional: clip.partial == null
+};
+
 struct AugArgs {
   const unsigned char* images;  // [Nd][H][W][3] uint8
   const int* labels;            // [Nd]
@@ -359,31 +433,12 @@ void ddp_conv_force_tile(int tile_plus_one, int stages);
 void ddp_conv_stamps_set(void* buf, int cap);
 #endif
 int ddp_pack_conv_weights(const ddp_amd::PackDesc* descs, int n, hipStream_t st);
-// ``sched``: learning rate from the device table; ``sched_advance`` = 1: this launch ends the
-// training step and stages the table's next step (LrSched::next = step + 1)
-int ddp_sgd_pack(const void* items, int n_items, const long long* descs, float* p, float* g,
-                 float* buf, float lr, float momentum, float wd, float grad_scale, int nesterov,
-                 int zero_grad, int* counter, int delta, const unsigned* skip,
-                 unsigned short* shadow, float* slot, unsigned* done, unsigned* signal,
-                 ddp_amd::LrSched* sched, int sched_advance, const void* lars_side,
-                 const void* lars_tensors, const void* lars_partial, float* lars_trust,
-                 float lars_eta, float lars_eps, const float* clip_partial, int clip_chunks,
-                 float clip_max_norm, float clip_eps, int clip_flags, float* clip_stats,
-                 hipStream_t st);
-// Gradient guard (optim.hip ClipArgs, optim/sgd.py max_grad_norm / skip_nonfinite):
-// ``clip_partial`` non-null selects the clipped instantiation of ddp_sgd_pack (plain or LARS) —
-// one float per 8192-element chunk of the WHOLE arena (``clip_chunks`` of them), sum
-// (g * grad_scale)^2 as written by ddp_grad_sumsq, launched before it (int4 items {arena offset,
-// count <= 8192, global chunk, -}, one block each); ``clip_flags``: 1 = clip to
-// ``clip_max_norm``, 2 = skip a step whose norm is not finite, 4 = this launch ends the step (a
-// skipped step is counted); ``clip_stats``: 4 words {norm, coefficient, skipped steps (u32), -}
+// the fused SGD + re-pack launch (UpdateLaunch above); -1: a LARS pointer or clip.stats missing
+int ddp_sgd_pack(const ddp_amd::UpdateLaunch* u, hipStream_t st);
+// the two per-chunk sums: int4 items {arena offset, count <= 8192, global chunk, -}, one block
+// each; ``partial`` as ClipArgs::partial (float) and LarsArgs::partial (float2)
 int ddp_grad_sumsq(const void* items, int n_items, const float* g, float grad_scale,
                    float* partial, hipStream_t st);
-// LARS (optim.hip LarsArgs, optim/lars.py): ``lars_side`` non-null selects the LARS instantiation
-// of ddp_sgd_pack — int2 per work item {parameter | -1, first item of its tensor}, ``lars_tensors``
-// int4 per parameter {first global chunk, chunks, adapted, -}, ``lars_partial`` float2 per global
-// chunk as written by ddp_lars_norms, launched before it on the same stream: int4 items
-// {arena offset, count <= 8192, global chunk, -}, one block each
 int ddp_lars_norms(const void* items, int n_items, const float* p, const float* g,
                    float grad_scale, void* partial, hipStream_t st);
 // tail of a pipelined step with sharded buckets: gathered small-tensor slots -> fp32 arena,

@@ -11,6 +11,8 @@
 // pack_conv_weights re-lays the fp32 master weights (PyTorch [K][C][R][S]) into the two bf16
 // MFMA operand layouts used by conv_igemm.hip: Wc [K][R][S][Cpad] (fwd) and Wt [C][R][S][K]
 // (dgrad); all conv tensors of the model in one launch (blockIdx.y = tensor).
+#include <type_traits>
+
 #include "common.h"
 #include "api.h"
 
@@ -54,22 +56,26 @@ __device__ __forceinline__ size_t master_index(const PackDesc& d, int k, int c, 
                 : (((size_t)k * d.Cr + c) * d.R + r) * d.S + s;
 }
 
+// Element i of Wc [k][r][s][c] from the master: bf16(p[k][c][r][s]), +0 in the padded channels.
+// Index: the index type of the caller's loop (its divisions stay as wide as they were).
+template <class Index>
+__device__ __forceinline__ unsigned short wc_from_master(const PackDesc& d, Index i) {
+  const int c = (int)(i % d.C);
+  const Index t1 = i / d.C;
+  const int s = (int)(t1 % d.S);
+  const Index t2 = t1 / d.S;
+  const int r = (int)(t2 % d.R);
+  const int k = (int)(t2 / d.R);
+  return f2bf(c < d.Cr ? d.p[master_index(d, k, c, r, s)] : 0.f);
+}
+
 __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
   const PackDesc d = t.d[blockIdx.y];
   const int rs = d.R * d.S;
   const size_t total = (size_t)d.K * rs * d.C;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += stride) {
-    if (d.wc) {  // i indexes Wc [k][r][s][c]
-      const int c = (int)(i % d.C);
-      const size_t t1 = i / d.C;
-      const int s = (int)(t1 % d.S);
-      const size_t t2 = t1 / d.S;
-      const int r = (int)(t2 % d.R);
-      const int k = (int)(t2 / d.R);
-      const float v = c < d.Cr ? d.p[master_index(d, k, c, r, s)] : 0.f;
-      d.wc[i] = f2bf(v);
-    }
+    if (d.wc) d.wc[i] = wc_from_master(d, i);
     if (d.wt) {  // i indexes Wt [c][r][s][k]
       const int k = (int)(i % d.K);
       const size_t t1 = i / d.K;
@@ -86,51 +92,34 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 // ---------------------------------------------------------------------------------------------
 // Fused SGD + weight re-pack: ONE launch updates the whole arena and writes the bf16 MFMA
 // operand copies of every conv weight from the freshly updated values (no second pass over the
-// fp32 weights). Work items (int4): {0, offset, count, -} = plain elementwise chunk;
-// {2, rel_offset, count, desc} = elementwise chunk of a conv weight stored [K][R][S][C] (the GPU
-// arena layout): its bf16 copy Wc has the same index order, so it is written in the same pass;
-// {1, desc, k0, c0} = one TK x TC x (R*S) tile of a conv weight that needs a layout change
-// (channel-padded input layer, or a [K][C][R][S] master), staged through LDS so that the Wc
-// ([k][r][s][c], c fastest) and optional Wt ([c][r][s][k], k fastest) writes are coalesced.
-// Conv descriptor (int64 x 12): {p_offset, K, Cr, C, R, S, wc_ptr, wt_ptr, krsc, -, -, -};
-// krsc selects the fp32 master layout ([K][R][S][Cr] vs [K][Cr][R][S]).
+// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD>, one block per work item (int4):
+//   {0, offset, count, -}        plain elementwise chunk;
+//   {2, rel_offset, count, desc} elementwise chunk of a conv weight stored [K][R][S][C] (the GPU
+//                                arena layout, C == Cr, or 1x1): its bf16 copy Wc has the same
+//                                index order, so it is written in the same pass (count multiple
+//                                of 4, base 4-aligned: arena tensors are 64-aligned);
+//   {1, desc, k0, c0}            one TK x TC x (R*S) tile of a conv weight that needs a layout
+//                                change (channel-padded input layer, or a [K][C][R][S] master),
+//                                staged through LDS so that the Wc ([k][r][s][c], c fastest) and
+//                                optional Wt ([c][r][s][k], k fastest) writes are coalesced;
+//   {3, offset, count, slot_offset | -1}  this rank's shard of a sharded bucket — SGD on the fp32
+//                                master + momentum, bf16 operand image of the new values
+//                                (``shadow``), fp32 send slot of the small tensors (offset, count
+//                                and slot_offset multiples of 4: 64-aligned tensors, shards of
+//                                n/w with n % 64 == 0 and w | 8);
+//   {4, offset, count, -}        clear gradients outside this rank's shard (count multiple of 4);
+//   {5, rel_offset, count, desc} operand re-pack only — the fp32 master was already updated by
+//                                the backward (conv_igemm.hip ConvArgs::sgd); bf16(p) into the
+//                                operand copy (as item 2).
+// Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs.
 constexpr int kTileElems = 9216;  // fp32 LDS tile (36 KB)
 
-__device__ __forceinline__ void tile_dims(int RS, int* TK, int* TC) {
+__host__ __device__ __forceinline__ void tile_dims(int RS, int* TK, int* TC) {
   if (RS == 1) { *TK = 64; *TC = 64; }
   else if (RS <= 9) { *TK = 32; *TC = 32; }
   else { *TK = 8; *TC = 16; }
 }
 
-struct SgdHyper {
-  float lr, momentum, wd, grad_scale;
-  int nesterov;
-  int zero_grad;  // write 0 to every gradient after use (replaces the next step's zero_grad fill)
-  int* counter;   // optional step counter (data cursor): += delta by one thread
-  int delta;
-  // optional error word (engine/step.py SegmentedDDPStep): non-zero when a device-side wait for
-  // a gradient bucket timed out — the update is then skipped instead of applying gradients
-  // that were never averaged (the host raises on the error at its next check)
-  const unsigned* skip;
-  // sharded update with a bf16 operand all-gather (parallel/zero.py ShardedBf16Update): item 3
-  // also stores bf16(new p) into ``shadow`` (the bf16 operand image of the arena, same element
-  // index) and, for the small fp32-wire tensors, the new p into ``slot`` (the all-gather send slot)
-  unsigned short* shadow;
-  float* slot;
-  // optional completion signal (engine/step.py SegmentedDDPStep, last bucket): the last block
-  // to finish (``done`` ticket, reset by it) release-increments ``signal`` — the step's
-  // "every parameter updated" flag without a separate signal launch
-  unsigned* done;
-  unsigned* signal;
-  // optional learning-rate schedule (api.h LrSched): every block reads this step's rate from the
-  // table instead of ``lr``; ``sched_advance``: this launch ends the training step — block 0
-  // stages the next step (``next``, read by no block here; a later launch makes it current)
-  LrSched* sched;
-  int sched_advance;
-};
-
-// Last-block-done hand-off: every block's writes are fenced, the block that takes the last
-// ticket resets the ticket and release-increments the flag (acquired by flag_wait_kernel).
 // The step's error word (SegmentedDDPStep: a device-side wait timed out), read ONCE per block:
 // every thread of the block takes the same branch, so no thread can leave while others still
 // wait at a barrier of a tile item or of last_block_done (the word may flip during the launch).
@@ -142,6 +131,8 @@ __device__ __forceinline__ bool block_skip(const unsigned* skip) {
   return s_skip != 0u;
 }
 
+// Last-block-done hand-off: every block's writes are fenced, the block that takes the last
+// ticket resets the ticket and release-increments the flag (acquired by flag_wait_kernel).
 __device__ __forceinline__ bool last_block_done(unsigned* done) {
   __syncthreads();
   __shared__ unsigned last;
@@ -186,111 +177,180 @@ __device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper
   }
 }
 
-// Gradient guard of the clipped instantiations (ClipArgs below): this step's verdict, the same
-// in every block of the launch.
-struct GuardState {
-  float norm, c;  // sqrt(sum (g * grad_scale)^2) over every parameter element; clip coefficient
-  int skipped;    // non-finite norm with skip_nonfinite: the launch only clears the gradients
-  float* stats;   // {norm, c, skipped steps (uint32), -}, stored by block 0
-  int count;      // this launch ends the step: a skipped step is counted
-};
-
-template <bool LARS, bool GUARD = false>
-__device__ void sgd_pack_body(const int4* __restrict__ items, const long long* __restrict__ descs,
-                              float* __restrict__ p, float* __restrict__ g,
-                              float* __restrict__ buf, const SgdHyper& h, float* tile,
-                              float trust, GuardState gd = GuardState{});
-
-__global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
-                                                       const long long* __restrict__ descs,
-                                                       float* __restrict__ p,
-                                                       float* __restrict__ g,
-                                                       float* __restrict__ buf, SgdHyper h) {
-  __shared__ float tile[kTileElems];
-  h.lr = sched_lr_block(h.sched, h.lr);
-  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
-  sgd_pack_body<false>(items, descs, p, g, buf, h, tile, 1.f);
-  if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
+// The update of four elements (16-byte aligned) on float4 registers: p and buf stored, +0 into
+// g under zero_grad; returns the new p.
+template <bool LARS>
+__device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, const SgdHyper& h,
+                                       float trust) {
+  float4 pv = *reinterpret_cast<float4*>(p);
+  const float4 gv = *reinterpret_cast<const float4*>(g);
+  float4 bv = *reinterpret_cast<float4*>(buf);
+  pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
+  pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
+  pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
+  pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
+  *reinterpret_cast<float4*>(p) = pv;
+  *reinterpret_cast<float4*>(buf) = bv;
+  if (h.zero_grad) *reinterpret_cast<float4*>(g) = make_float4(0.f, 0.f, 0.f, 0.f);
+  return pv;
 }
+
+__device__ __forceinline__ uint2 bf16x4(const float4& v) {
+  return make_uint2((unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16),
+                    (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16));
+}
+
+// Arena offset of an elementwise item's first element (kinds 0, 3, 4: absolute; 2, 5: relative
+// to their conv master).
+__device__ __forceinline__ size_t elem_offset(const int4& it, const ConvDesc* __restrict__ descs) {
+  return (it.x == 2 || it.x == 5 ? (size_t)descs[it.w].p_offset : 0) + (unsigned)it.y;
+}
+
+// A tile item {1, desc, k0, c0}: TK x TC x (R*S) weights from (k0, c0), cut at the tensor's edges.
+struct Tile {
+  size_t poff;
+  int K, Cr, C, RS, TC, k0, c0;
+  int tk, tcr, tcp;  // filters, real channels and padded channels (Wc width) of this tile
+  bool krsc;
+  __device__ Tile(const ConvDesc& d, const int4& it)
+      : poff((size_t)d.p_offset), K((int)d.K), Cr((int)d.Cr), C((int)d.C),
+        RS((int)d.R * (int)d.S), k0(it.z), c0(it.w), krsc(d.krsc != 0) {
+    int TK;
+    tile_dims(RS, &TK, &TC);
+    tk = min(TK, K - k0);
+    tcr = max(0, min(TC, Cr - c0));
+    tcp = min(TC, C - c0);
+  }
+  // LDS tile layout [kl][cl][rs]
+  __device__ int lds(int kl, int cl, int rs) const { return (kl * TC + cl) * RS + rs; }
+  // f(arena index, LDS index) for every master element of the tile's real channels, in runs of
+  // contiguous floats: tcr * RS of p[k][c][r][s], or tcr channels per (k, r, s) of p[k][r][s][c].
+  // The update and the skipped step's clear both walk the tile through this.
+  template <class F>
+  __device__ __forceinline__ void for_each_master(F&& f) const {
+    if (!krsc) {
+      const int run = tcr * RS;
+      for (int idx = threadIdx.x; idx < tk * run; idx += 256) {
+        const int kl = idx / run, e = idx - kl * run;
+        f(poff + (size_t)(k0 + kl) * Cr * RS + (size_t)c0 * RS + e, kl * TC * RS + e);
+      }
+    } else {
+      for (int idx = threadIdx.x; idx < tk * RS * tcr; idx += 256) {
+        const int cl = idx % tcr, t = idx / tcr;
+        const int rs = t % RS, kl = t / RS;
+        f(poff + ((size_t)(k0 + kl) * RS + rs) * Cr + c0 + cl, lds(kl, cl, rs));
+      }
+    }
+  }
+};
 
 // ---------------------------------------------------------------------------------------------
 // LARS (You et al. 2017; optim/lars.py): every adapted tensor's update is multiplied by its
 // trust ratio eta * |w| / (|g * grad_scale| + wd * |w| + eps), both norms over the tensor's own
-// elements. Two launches, no float atomics, so the result does not depend on block scheduling:
-//   1) lars_norms_kernel: one block per 8192-element chunk (the chunking of the SGD items) stores
-//      {sum p^2, sum (g * grad_scale)^2} of its chunk into the slot of the chunk's GLOBAL number
+// elements. Gradient guard (optim/sgd.py max_grad_norm / skip_nonfinite): clipping by the norm
+// of the whole gradient, and skipping a step whose norm is not finite. The update launch
+// consumes and clears the gradient in one pass and runs inside a replayed graph, so both live
+// here, in two launches each, no float atomics, so the result does not depend on block scheduling:
+//   1) chunk_sums_kernel<WITH_P>: one block per 8192-element chunk (the chunking of the SGD
+//      items) stores {sum p^2, sum (g * grad_scale)^2} (LARS, float2) or sum (g * grad_scale)^2
+//      alone (the guard, float: half the bytes) into the slot of the chunk's GLOBAL number
 //      (numbered over the whole arena: per-bucket launches on different streams never share one);
-//   2) lars_pack_kernel, the LARS instantiation of the fused SGD + re-pack body: wave 0 of every
-//      block sums its tensor's partials in one fixed order (lane l adds chunks l, l + 64, ...
-//      serially, then wave_sum), computes the ratio and broadcasts it through LDS; the block
-//      that owns the tensor's first work item also stores it for the host (LARS.trust_ratios).
-// The norms are read from memory the first launch wrote, so a zero_grad in the second one is safe.
-struct LarsArgs {
-  const int2* side;       // per work item: {parameter index | -1 (no ratio: item 5), first item}
-  const int4* tensors;    // per parameter: {first global chunk, chunks, adapted, -}
-  const float2* partial;  // per global chunk: {sum p^2, sum (g * grad_scale)^2}
-  float* trust;           // per parameter (written)
-  float eta, eps;
+//   2) the prologue of sgd_pack_kernel: wave 0 of every block sums partials in one fixed order
+//      (lane l adds chunks l, l + 64, ... serially, then wave_sum) and broadcasts the result
+//      through LDS — every block of every launch gets the same bits.
+//      LARS: its tensor's partials give the ratio; the block that owns the tensor's first work
+//      item also stores it for the host (LARS.trust_ratios).
+//      GUARD: ALL partials of the arena give
+//          norm = sqrt(S);  c = min(1, max_norm / (norm + eps)) (1 without a max_norm)
+//      and the body runs with grad_scale * c. c == 1.0 reproduces the plain update bit for bit.
+//      A norm that is not finite (an Inf / NaN gradient, or S beyond fp32) with skip_nonfinite
+//      set: item kinds 0-3 only clear their gradient range (with zero_grad; a stale NaN would
+//      poison every later step, the kernels accumulate into the arena), kinds 4 and 5 run as they
+//      are; the data cursor, the completion signal and the schedule staging go on as in any
+//      step. The ``skip`` word keeps precedence: with it set nothing is touched or recorded.
+// The sums are read from memory the first launch wrote, so a zero_grad in the second one is safe.
+constexpr int kNormChunk = 8192;  // elements per chunk block (optim/sgd.py FusedSGD.CHUNK)
+
+struct NoP {};
+struct WithP { const float* p; };
+template <bool WITH_P>
+struct ChunkSumArgs : std::conditional_t<WITH_P, WithP, NoP> {
+  const int4* items;  // {arena offset (multiple of 4), count <= kNormChunk, global chunk number, -}
+  const float* g;
+  float grad_scale;
+  std::conditional_t<WITH_P, float2, float>* partial;
 };
 
-constexpr int kNormChunk = 8192;  // elements per norm block (optim/lars.py LARS.CHUNK)
-
-__global__ __launch_bounds__(256) void lars_norms_kernel(const int4* __restrict__ items,
-                                                         const float* __restrict__ p,
-                                                         const float* __restrict__ g,
-                                                         float grad_scale,
-                                                         float2* __restrict__ partial) {
-  // {arena offset (multiple of 4), count <= kNormChunk, global chunk number, -}
-  const int4 it = items[blockIdx.x];
+template <bool WITH_P>
+__global__ __launch_bounds__(256) void chunk_sums_kernel(ChunkSumArgs<WITH_P> a) {
+  const int4 it = a.items[blockIdx.x];
   const size_t off = (size_t)(unsigned)it.x;
   const int cnt = it.y, n4 = cnt >> 2;
   const int tid = threadIdx.x;
-  const float4* p4 = reinterpret_cast<const float4*>(p + off);
-  const float4* g4 = reinterpret_cast<const float4*>(g + off);
+  const float* __restrict__ p = nullptr;  // (stays null and unread without WITH_P)
+  if constexpr (WITH_P) p = a.p + off;
+  const float* __restrict__ g = a.g + off;
+  const float4* p4 = reinterpret_cast<const float4*>(p);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
   constexpr int kIter = kNormChunk / (256 * 4);
+  // (The two forms of the zero below are what each instantiation was compiled from before the
+  // two kernels became one, and they stay: with the named zero the compiler splits the two-operand
+  // loads into dwords at 74 VGPRs, 6 waves per SIMD; with the temporary it keeps them 16 bytes
+  // wide at 92 VGPRs, 5 waves. Which is faster was not measured.)
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 pv[kIter], gv[kIter];
+  float4 pv[WITH_P ? kIter : 1], gv[kIter];
 #pragma unroll
   for (int j = 0; j < kIter; ++j) {  // every 16-byte load of the chunk in flight at once
     const int i = tid + 256 * j;
-    pv[j] = i < n4 ? p4[i] : z;
-    gv[j] = i < n4 ? g4[i] : z;
+    if constexpr (WITH_P) {
+      pv[j] = i < n4 ? p4[i] : z;
+      gv[j] = i < n4 ? g4[i] : z;
+    } else {
+      gv[j] = i < n4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
   }
   float sp = 0.f, sg = 0.f;  // one serial fma chain per thread: 4 * kIter (+ 1 tail) terms
 #pragma unroll
   for (int j = 0; j < kIter; ++j) {
-    const float* pp = &pv[j].x;
+    const float* pp = &pv[WITH_P ? j : 0].x;
     const float* gg = &gv[j].x;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float gs = gg[e] * grad_scale;
-      sp = __builtin_fmaf(pp[e], pp[e], sp);
+      const float gs = gg[e] * a.grad_scale;
+      if constexpr (WITH_P) sp = __builtin_fmaf(pp[e], pp[e], sp);
       sg = __builtin_fmaf(gs, gs, sg);
     }
   }
   const int t = (n4 << 2) + tid;  // scalar tail: numel not a multiple of 4
   if (t < cnt) {
-    const float pt = p[off + t], gs = g[off + t] * grad_scale;
-    sp = __builtin_fmaf(pt, pt, sp);
+    const float gs = g[t] * a.grad_scale;
+    if constexpr (WITH_P) sp = __builtin_fmaf(p[t], p[t], sp);
     sg = __builtin_fmaf(gs, gs, sg);
   }
-  sp = wave_sum(sp);
+  if constexpr (WITH_P) sp = wave_sum(sp);
   sg = wave_sum(sg);
-  __shared__ float2 s_w[4];
-  if ((tid & 63) == 0) s_w[tid >> 6] = make_float2(sp, sg);
+  __shared__ std::conditional_t<WITH_P, float2, float> s_w[4];  // per wave
+  if ((tid & 63) == 0) {
+    if constexpr (WITH_P) s_w[tid >> 6] = make_float2(sp, sg);
+    else s_w[tid >> 6] = sg;
+  }
   __syncthreads();
   if (tid == 0) {
-    partial[it.z] = make_float2(((s_w[0].x + s_w[1].x) + s_w[2].x) + s_w[3].x,
-                                ((s_w[0].y + s_w[1].y) + s_w[2].y) + s_w[3].y);
+    if constexpr (WITH_P) {
+      a.partial[it.z] = make_float2(((s_w[0].x + s_w[1].x) + s_w[2].x) + s_w[3].x,
+                                    ((s_w[0].y + s_w[1].y) + s_w[2].y) + s_w[3].y);
+    } else {
+      a.partial[it.z] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+    }
   }
 }
 
 // This block's trust ratio (1.0: excluded tensor, zero norm, item without an update). Every
 // condition but the partial loop's trip count is uniform over the block.
-// GUARD (the clipped instantiation): clip first — the gradient norm is that of the clipped
-// gradient, c * gn, with no second pass: sum (g gs c)^2 = c^2 * sum (g gs)^2.
-template <bool GUARD = false>
-__device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd, float c = 1.f) {
+// GUARD: clip first — the gradient norm is that of the clipped gradient, c * gn, with no second
+// pass: sum (g gs c)^2 = c^2 * sum (g gs)^2.
+template <bool GUARD>
+__device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd, float c) {
   __shared__ float s_trust;
   if (threadIdx.x < 64) {
     const int2 sd = a.side[blockIdx.x];
@@ -317,86 +377,14 @@ __device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd, f
   return s_trust;
 }
 
-__global__ __launch_bounds__(256) void lars_pack_kernel(const int4* __restrict__ items,
-                                                        const long long* __restrict__ descs,
-                                                        float* __restrict__ p,
-                                                        float* __restrict__ g,
-                                                        float* __restrict__ buf, SgdHyper h,
-                                                        LarsArgs la) {
-  __shared__ float tile[kTileElems];
-  h.lr = sched_lr_block(h.sched, h.lr);
-  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
-  const float trust = lars_trust_block(la, h.wd);
-  sgd_pack_body<true>(items, descs, p, g, buf, h, tile, trust);
-  if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Gradient clipping and non-finite step skipping (optim/sgd.py max_grad_norm / skip_nonfinite).
-// The update launch consumes and clears the gradient in one pass and runs inside a replayed
-// graph, so the guard lives here, in two launches like LARS:
-//   1) grad_sumsq_kernel: one block per 8192-element chunk of every parameter (the chunking and
-//      the whole-arena chunk numbers of lars_norms_kernel) stores sum (g * grad_scale)^2 of its
-//      chunk: half the bytes of the LARS norms pass, no float atomics;
-//   2) the clipped instantiations of the fused update: wave 0 of every block sums ALL partials of
-//      the arena in one fixed order (lane l adds chunks l, l + 64, ... serially, then wave_sum) —
-//      every block of every launch gets the same bits —
-//          norm = sqrt(S);  c = min(1, max_norm / (norm + eps)) (1 without a max_norm)
-//      and the body runs with grad_scale * c. c == 1.0 reproduces the plain update bit for bit.
-//      A norm that is not finite (an Inf / NaN gradient, or S beyond fp32) with skip_nonfinite
-//      set: item kinds 0-3 only clear their gradient range (with zero_grad; a stale NaN would
-//      poison every later step, the kernels accumulate into the arena), kinds 4 and 5 run as they
-//      are; the data cursor, the completion signal and the schedule staging go on as in any
-//      step. The ``skip`` word keeps precedence: with it set nothing is touched or recorded.
-struct ClipArgs {
-  const float* partial;  // per global chunk: sum (g * grad_scale)^2 (grad_sumsq_kernel)
-  int n_chunks;          // chunks of the whole arena
-  float max_norm, eps;
-  int flags;             // 1: clip to max_norm, 2: skip a non-finite step, 4: count a skipped step
-  float* stats;          // GuardState::stats
+// The guard's verdict of this step, the same in every block of the launch.
+struct GuardState {
+  float norm, c;  // sqrt(sum (g * grad_scale)^2) over every parameter element; clip coefficient
+  int skipped;    // non-finite norm with skip_nonfinite: the launch only clears the gradients
+  float* stats;   // ClipArgs::stats
+  int count;      // this launch ends the step: a skipped step is counted
 };
 
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const int4* __restrict__ items,
-                                                         const float* __restrict__ g,
-                                                         float grad_scale,
-                                                         float* __restrict__ partial) {
-  // {arena offset (multiple of 4), count <= kNormChunk, global chunk number, -}
-  const int4 it = items[blockIdx.x];
-  const size_t off = (size_t)(unsigned)it.x;
-  const int cnt = it.y, n4 = cnt >> 2;
-  const int tid = threadIdx.x;
-  const float4* g4 = reinterpret_cast<const float4*>(g + off);
-  constexpr int kIter = kNormChunk / (256 * 4);
-  float4 gv[kIter];
-#pragma unroll
-  for (int j = 0; j < kIter; ++j) {  // every 16-byte load of the chunk in flight at once
-    const int i = tid + 256 * j;
-    gv[j] = i < n4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  float sg = 0.f;  // one serial fma chain per thread: 4 * kIter (+ 1 tail) terms
-#pragma unroll
-  for (int j = 0; j < kIter; ++j) {
-    const float* gg = &gv[j].x;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gs = gg[e] * grad_scale;
-      sg = __builtin_fmaf(gs, gs, sg);
-    }
-  }
-  const int t = (n4 << 2) + tid;  // scalar tail: numel not a multiple of 4
-  if (t < cnt) {
-    const float gs = g[off + t] * grad_scale;
-    sg = __builtin_fmaf(gs, gs, sg);
-  }
-  sg = wave_sum(sg);
-  __shared__ float s_w[4];
-  if ((tid & 63) == 0) s_w[tid >> 6] = sg;
-  __syncthreads();
-  if (tid == 0) partial[it.z] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
-// This step's verdict, computed by wave 0 of every block from the same partials in the same
-// order and broadcast through LDS (as lars_trust_block).
 __device__ __forceinline__ GuardState clip_block(const ClipArgs& a) {
   __shared__ float s_norm, s_c;
   __shared__ int s_skipped;
@@ -420,47 +408,22 @@ __device__ __forceinline__ GuardState clip_block(const ClipArgs& a) {
 }
 
 // A skipped step's share of a work item of kind 0-3: its gradient range, cleared.
-__device__ __forceinline__ void guard_clear(const int4& it, const long long* __restrict__ descs,
+__device__ __forceinline__ void guard_clear(const int4& it, const ConvDesc* __restrict__ descs,
                                             float* __restrict__ g) {
-  const int tid = threadIdx.x;
-  if (it.x == 0 || it.x == 3) {
-    float* gp = g + (size_t)(unsigned)it.y;
-    for (int i = tid; i < it.z; i += 256) gp[i] = 0.f;
+  if (it.x == 1) {
+    Tile(descs[it.y], it).for_each_master([&](size_t gi, int) { g[gi] = 0.f; });
     return;
   }
-  if (it.x == 2) {
-    float* gp = g + (size_t)descs[12 * it.w] + (unsigned)it.y;
-    for (int i = tid; i < it.z; i += 256) gp[i] = 0.f;
-    return;
-  }
-  const long long* d = descs + 12 * it.y;  // kind 1: the tile's real channels (as the body)
-  const size_t poff = (size_t)d[0];
-  const int K = (int)d[1], Cr = (int)d[2], RS = (int)d[4] * (int)d[5];
-  int TK, TC;
-  tile_dims(RS, &TK, &TC);
-  const int k0 = it.z, c0 = it.w;
-  const int tk = min(TK, K - k0);
-  const int tcr = max(0, min(TC, Cr - c0));
-  if (d[8] == 0) {
-    const int run = tcr * RS;
-    for (int idx = tid; idx < tk * run; idx += 256) {
-      const int kl = idx / run, e = idx - kl * run;
-      g[poff + (size_t)(k0 + kl) * Cr * RS + (size_t)c0 * RS + e] = 0.f;
-    }
-  } else {
-    for (int idx = tid; idx < tk * RS * tcr; idx += 256) {
-      const int cl = idx % tcr, t = idx / tcr;
-      const int rs = t % RS, kl = t / RS;
-      g[poff + ((size_t)(k0 + kl) * RS + rs) * Cr + c0 + cl] = 0.f;
-    }
-  }
+  float* gp = g + elem_offset(it, descs);
+  for (int i = threadIdx.x; i < it.z; i += 256) gp[i] = 0.f;
 }
 
 template <bool LARS, bool GUARD>
-__device__ void sgd_pack_body(const int4* __restrict__ items, const long long* __restrict__ descs,
-                              float* __restrict__ p, float* __restrict__ g,
-                              float* __restrict__ buf, const SgdHyper& h, float* tile,
-                              float trust, GuardState gd) {
+__device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
+                                              const ConvDesc* __restrict__ descs,
+                                              float* __restrict__ p, float* __restrict__ g,
+                                              float* __restrict__ buf, const SgdHyper& h,
+                                              float* tile, float trust, const GuardState& gd) {
   const int4 it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
@@ -479,200 +442,121 @@ __device__ void sgd_pack_body(const int4* __restrict__ items, const long long* _
       return;
     }
   }
-  if (it.x == 0) {
-    const size_t off = (size_t)(unsigned)it.y;
-    const int cnt = it.z;
-    for (int i = tid * 4; i < cnt; i += 256 * 4) {
-      if (i + 4 <= cnt && ((off + i) & 3) == 0) {
-        float4 pv = *reinterpret_cast<float4*>(p + off + i);
-        const float4 gv = *reinterpret_cast<const float4*>(g + off + i);
-        float4 bv = *reinterpret_cast<float4*>(buf + off + i);
-        pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
-        pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
-        pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
-        pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
-        *reinterpret_cast<float4*>(p + off + i) = pv;
-        *reinterpret_cast<float4*>(buf + off + i) = bv;
-        if (h.zero_grad) *reinterpret_cast<float4*>(g + off + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-        for (int e = i; e < min(cnt, i + 4); ++e) {
-          float b = buf[off + e];
-          p[off + e] = sgd1<LARS>(p[off + e], g[off + e], b, h, trust);
-          buf[off + e] = b;
-          if (h.zero_grad) g[off + e] = 0.f;
+  const int cnt = it.z;  // (elementwise items)
+  switch (it.x) {
+    case 0: {
+      const size_t off = elem_offset(it, descs);
+      for (int i = tid * 4; i < cnt; i += 256 * 4) {
+        if (i + 4 <= cnt && ((off + i) & 3) == 0) {
+          sgd4<LARS>(p + off + i, g + off + i, buf + off + i, h, trust);
+        } else {
+          for (int e = i; e < min(cnt, i + 4); ++e) {
+            float b = buf[off + e];
+            p[off + e] = sgd1<LARS>(p[off + e], g[off + e], b, h, trust);
+            buf[off + e] = b;
+            if (h.zero_grad) g[off + e] = 0.f;
+          }
         }
       }
+      break;
     }
-    return;
-  }
-  if (it.x == 3) {
-    // {3, offset, count, slot_offset | -1}: this rank's shard of a sharded bucket — SGD on the
-    // fp32 master + momentum, bf16 operand image of the new values, fp32 send slot of the
-    // small tensors (offset, count and slot_offset multiples of 4: 64-aligned tensors, shards
-    // of n/w with n % 64 == 0 and w | 8)
-    const size_t off = (size_t)(unsigned)it.y;
-    const int cnt = it.z;
-    float* slot = it.w >= 0 && h.slot ? h.slot + it.w : nullptr;
-    for (int i = tid * 4; i < cnt; i += 256 * 4) {
-      float4 pv = *reinterpret_cast<float4*>(p + off + i);
-      const float4 gv = *reinterpret_cast<const float4*>(g + off + i);
-      float4 bv = *reinterpret_cast<float4*>(buf + off + i);
-      pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
-      pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
-      pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
-      pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
-      *reinterpret_cast<float4*>(p + off + i) = pv;
-      *reinterpret_cast<float4*>(buf + off + i) = bv;
-      if (h.zero_grad) *reinterpret_cast<float4*>(g + off + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (h.shadow) {
-        uint2 pk;
-        pk.x = (unsigned)f2bf(pv.x) | ((unsigned)f2bf(pv.y) << 16);
-        pk.y = (unsigned)f2bf(pv.z) | ((unsigned)f2bf(pv.w) << 16);
-        *reinterpret_cast<uint2*>(h.shadow + off + i) = pk;
+    case 3: {
+      const size_t off = elem_offset(it, descs);
+      float* slot = it.w >= 0 && h.slot ? h.slot + it.w : nullptr;
+      for (int i = tid * 4; i < cnt; i += 256 * 4) {
+        const float4 pv = sgd4<LARS>(p + off + i, g + off + i, buf + off + i, h, trust);
+        if (h.shadow) *reinterpret_cast<uint2*>(h.shadow + off + i) = bf16x4(pv);
+        if (slot) *reinterpret_cast<float4*>(slot + i) = pv;
       }
-      if (slot) *reinterpret_cast<float4*>(slot + i) = pv;
+      break;
     }
-    return;
-  }
-  if (it.x == 4) {
-    // {4, offset, count, -}: clear gradients outside this rank's shard (count multiple of 4)
-    const size_t off = (size_t)(unsigned)it.y;
-    for (int i = tid * 4; i < it.z; i += 256 * 4)
-      *reinterpret_cast<float4*>(g + off + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    return;
-  }
-  if (it.x == 5) {
-    // {5, offset in the tensor, count, desc}: operand re-pack only — the fp32 master was already
-    // updated by the backward (conv_igemm.hip ConvArgs::sgd); bf16(p) into the operand copy
-    // (same index order as item 2; count multiple of 4)
-    const long long* d = descs + 12 * it.w;
-    const size_t base = (size_t)d[0] + (unsigned)it.y;
-    unsigned short* wc = reinterpret_cast<unsigned short*>(d[6]) + (unsigned)it.y;
-    for (int i = tid * 4; i < it.z; i += 256 * 4) {
-      const float4 pv = *reinterpret_cast<const float4*>(p + base + i);
-      uint2 pk;
-      pk.x = (unsigned)f2bf(pv.x) | ((unsigned)f2bf(pv.y) << 16);
-      pk.y = (unsigned)f2bf(pv.z) | ((unsigned)f2bf(pv.w) << 16);
-      *reinterpret_cast<uint2*>(wc + i) = pk;
+    case 4: {
+      const size_t off = elem_offset(it, descs);
+      for (int i = tid * 4; i < cnt; i += 256 * 4)
+        *reinterpret_cast<float4*>(g + off + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+      break;
     }
-    return;
-  }
-  if (it.x == 2) {
-    // conv weight whose bf16 operand copy has the master's own index order ([K][R][S][C] with
-    // C == Cr, or 1x1): elementwise update + bf16 store, no LDS staging
-    const long long* d = descs + 12 * it.w;
-    const size_t base = (size_t)d[0] + (unsigned)it.y;
-    unsigned short* wc = reinterpret_cast<unsigned short*>(d[6]) + (unsigned)it.y;
-    const int cnt = it.z;  // multiple of 4, base 4-aligned (arena tensors are 64-aligned)
-    for (int i = tid * 4; i < cnt; i += 256 * 4) {
-      float4 pv = *reinterpret_cast<float4*>(p + base + i);
-      const float4 gv = *reinterpret_cast<const float4*>(g + base + i);
-      float4 bv = *reinterpret_cast<float4*>(buf + base + i);
-      pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
-      pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
-      pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
-      pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
-      *reinterpret_cast<float4*>(p + base + i) = pv;
-      *reinterpret_cast<float4*>(buf + base + i) = bv;
-      if (h.zero_grad) *reinterpret_cast<float4*>(g + base + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-      uint2 pk;
-      pk.x = (unsigned)f2bf(pv.x) | ((unsigned)f2bf(pv.y) << 16);
-      pk.y = (unsigned)f2bf(pv.z) | ((unsigned)f2bf(pv.w) << 16);
-      *reinterpret_cast<uint2*>(wc + i) = pk;
+    case 2: {  // no LDS staging: the operand copy has the master's own index order
+      const size_t base = elem_offset(it, descs);
+      unsigned short* wc = descs[it.w].wc + (unsigned)it.y;
+      for (int i = tid * 4; i < cnt; i += 256 * 4) {
+        const float4 pv = sgd4<LARS>(p + base + i, g + base + i, buf + base + i, h, trust);
+        *reinterpret_cast<uint2*>(wc + i) = bf16x4(pv);
+      }
+      break;
     }
-    return;
-  }
-  const long long* d = descs + 12 * it.y;
-  const size_t poff = (size_t)d[0];
-  const int K = (int)d[1], Cr = (int)d[2], C = (int)d[3], R = (int)d[4], S = (int)d[5];
-  unsigned short* wc = reinterpret_cast<unsigned short*>(d[6]);
-  unsigned short* wt = reinterpret_cast<unsigned short*>(d[7]);
-  const int RS = R * S;
-  int TK, TC;
-  tile_dims(RS, &TK, &TC);
-  const int k0 = it.z, c0 = it.w;
-  const int tk = min(TK, K - k0);
-  const int tcr = max(0, min(TC, Cr - c0));  // real channels in this tile
-  const int tcp = min(TC, C - c0);           // padded channels in this tile (Wc width)
-  const bool krsc = d[8] != 0;
-  if (!krsc) {
-    // 1) SGD on p[k][c][r][s] for the tile's real channels; runs of tcr*RS contiguous floats
-    const int run = tcr * RS;
-    for (int idx = tid; idx < tk * run; idx += 256) {
-      const int kl = idx / run, e = idx - kl * run;
-      const size_t gi = poff + (size_t)(k0 + kl) * Cr * RS + (size_t)c0 * RS + e;
-      float b = buf[gi];
-      const float np = sgd1<LARS>(p[gi], g[gi], b, h, trust);
-      p[gi] = np;
-      buf[gi] = b;
-      if (h.zero_grad) g[gi] = 0.f;
-      tile[kl * TC * RS + e] = np;  // tile layout [kl][cl][rs]
+    case 5: {
+      const size_t base = elem_offset(it, descs);
+      unsigned short* wc = descs[it.w].wc + (unsigned)it.y;
+      for (int i = tid * 4; i < cnt; i += 256 * 4)
+        *reinterpret_cast<uint2*>(wc + i) = bf16x4(*reinterpret_cast<const float4*>(p + base + i));
+      break;
     }
-  } else {
-    // 1) SGD on p[k][r][s][c]: runs of tcr contiguous channels per (k, r, s)
-    for (int idx = tid; idx < tk * RS * tcr; idx += 256) {
-      const int cl = idx % tcr, t = idx / tcr;
-      const int rs = t % RS, kl = t / RS;
-      const size_t gi = poff + ((size_t)(k0 + kl) * RS + rs) * Cr + c0 + cl;
-      float b = buf[gi];
-      const float np = sgd1<LARS>(p[gi], g[gi], b, h, trust);
-      p[gi] = np;
-      buf[gi] = b;
-      if (h.zero_grad) g[gi] = 0.f;
-      tile[kl * TC * RS + cl * RS + rs] = np;
-    }
-  }
-  __syncthreads();
-  // 2) Wc[k][r][s][c] (c fastest, zero for padded channels)
-  if (wc) {
-    for (int idx = tid; idx < tk * RS * tcp; idx += 256) {
-      const int cl = idx % tcp, t = idx / tcp;
-      const int rs = t % RS, kl = t / RS;
-      const float v = cl < tcr ? tile[(kl * TC + cl) * RS + rs] : 0.f;
-      wc[((size_t)(k0 + kl) * RS + rs) * C + c0 + cl] = f2bf(v);
-    }
-  }
-  // 3) Wt[c][r][s][k] (k fastest)
-  if (wt) {
-    for (int idx = tid; idx < tcr * RS * tk; idx += 256) {
-      const int kl = idx % tk, t = idx / tk;
-      const int rs = t % RS, cl = t / RS;
-      wt[((size_t)(c0 + cl) * RS + rs) * K + k0 + kl] = f2bf(tile[(kl * TC + cl) * RS + rs]);
+    case 1: {
+      const ConvDesc& d = descs[it.y];
+      const Tile t(d, it);
+      // 1) SGD on the master for the tile's real channels, new values into the LDS tile
+      t.for_each_master([&](size_t gi, int li) {
+        float b = buf[gi];
+        const float np = sgd1<LARS>(p[gi], g[gi], b, h, trust);
+        p[gi] = np;
+        buf[gi] = b;
+        if (h.zero_grad) g[gi] = 0.f;
+        tile[li] = np;
+      });
+      __syncthreads();
+      // 2) Wc[k][r][s][c] (c fastest, zero for padded channels)
+      if (d.wc) {
+        for (int idx = tid; idx < t.tk * t.RS * t.tcp; idx += 256) {
+          const int cl = idx % t.tcp, q = idx / t.tcp;
+          const int rs = q % t.RS, kl = q / t.RS;
+          const float v = cl < t.tcr ? tile[t.lds(kl, cl, rs)] : 0.f;
+          d.wc[((size_t)(t.k0 + kl) * t.RS + rs) * t.C + t.c0 + cl] = f2bf(v);
+        }
+      }
+      // 3) Wt[c][r][s][k] (k fastest)
+      if (d.wt) {
+        for (int idx = tid; idx < t.tcr * t.RS * t.tk; idx += 256) {
+          const int kl = idx % t.tk, q = idx / t.tk;
+          const int rs = q % t.RS, cl = q / t.RS;
+          d.wt[((size_t)(t.c0 + cl) * t.RS + rs) * t.K + t.k0 + kl] = f2bf(tile[t.lds(kl, cl, rs)]);
+        }
+      }
+      break;
     }
   }
 }
 
-// The clipped instantiations of the two kernels above (ClipArgs): the same launch, body and
-// arguments, run with grad_scale * c.
-__global__ __launch_bounds__(256) void sgd_clip_pack_kernel(const int4* __restrict__ items,
-                                                            const long long* __restrict__ descs,
-                                                            float* __restrict__ p,
-                                                            float* __restrict__ g,
-                                                            float* __restrict__ buf, SgdHyper h,
-                                                            ClipArgs ca) {
-  __shared__ float tile[kTileElems];
-  h.lr = sched_lr_block(h.sched, h.lr);
-  if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
-  const GuardState gd = clip_block(ca);
-  h.grad_scale *= gd.c;
-  sgd_pack_body<false, true>(items, descs, p, g, buf, h, tile, 1.f, gd);
-  if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
-}
+// The kernel's arguments behind the tables and arenas (their __restrict__ keeps the table reads
+// scalar): SgdHyper, then LarsArgs and ClipArgs only in the instantiations that read them (an
+// empty base takes no kernarg bytes; an empty struct argument would).
+struct NoLars {};
+struct NoClip {};
+template <bool LARS, bool GUARD>
+struct UpdateArgs : SgdHyper, std::conditional_t<LARS, LarsArgs, NoLars>,
+                    std::conditional_t<GUARD, ClipArgs, NoClip> {};
+static_assert(sizeof(UpdateArgs<false, false>) == 96 && sizeof(UpdateArgs<false, true>) == 128 &&
+              sizeof(UpdateArgs<true, false>) == 136 && sizeof(UpdateArgs<true, true>) == 168,
+              "kernarg bytes of the four instantiations");
 
-__global__ __launch_bounds__(256) void lars_clip_pack_kernel(const int4* __restrict__ items,
-                                                             const long long* __restrict__ descs,
-                                                             float* __restrict__ p,
-                                                             float* __restrict__ g,
-                                                             float* __restrict__ buf, SgdHyper h,
-                                                             LarsArgs la, ClipArgs ca) {
+template <bool LARS, bool GUARD>
+__global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
+                                                       const ConvDesc* __restrict__ descs,
+                                                       float* __restrict__ p,
+                                                       float* __restrict__ g,
+                                                       float* __restrict__ buf,
+                                                       UpdateArgs<LARS, GUARD> a) {
   __shared__ float tile[kTileElems];
+  SgdHyper h = a;
   h.lr = sched_lr_block(h.sched, h.lr);
   if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
-  const GuardState gd = clip_block(ca);
+  GuardState gd{0.f, 1.f, 0, nullptr, 0};
+  if constexpr (GUARD) gd = clip_block(a);
+  float trust = 1.f;
   // (a skipped step leaves the stored ratios as they are)
-  const float trust = gd.skipped ? 1.f : lars_trust_block<true>(la, h.wd, gd.c);
-  h.grad_scale *= gd.c;
-  sgd_pack_body<true, true>(items, descs, p, g, buf, h, tile, trust, gd);
+  if constexpr (LARS) trust = GUARD && gd.skipped ? 1.f : lars_trust_block<GUARD>(a, h.wd, gd.c);
+  if constexpr (GUARD) h.grad_scale *= gd.c;
+  sgd_pack_body<LARS, GUARD>(items, descs, p, g, buf, h, tile, trust, gd);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
@@ -707,15 +591,8 @@ __global__ __launch_bounds__(256) void shard_tail_kernel(TailArgs a) {
   if (!skipped) {
     for (int q = 0; q < a.n_pack; ++q) {
       const PackDesc& d = a.pack[q];
-      const int rs = d.R * d.S;
-      const int total = d.K * rs * d.C;
-      for (int i = threadIdx.x; i < total; i += 256) {  // Wc [k][r][s][c], zero padded c
-        const int c = i % d.C, t1 = i / d.C;
-        const int sx = t1 % d.S, t2 = t1 / d.S;
-        const int r = t2 % d.R, k = t2 / d.R;
-        const float v = c < d.Cr ? d.p[master_index(d, k, c, r, sx)] : 0.f;
-        d.wc[i] = f2bf(v);
-      }
+      const int total = d.K * d.R * d.S * d.C;
+      for (int i = threadIdx.x; i < total; i += 256) d.wc[i] = wc_from_master(d, i);
     }
     __syncthreads();
     __threadfence();
@@ -731,6 +608,29 @@ __global__ void counter_add_kernel(int* c, int delta, LrSched* sched, int sched_
   if (sched_mode == 1) sched_stage(sched);
   const unsigned k = __hip_atomic_load(&sched->next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(&sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool LARS, bool GUARD>
+static int launch_update(const UpdateLaunch& u, hipStream_t st) {
+  UpdateArgs<LARS, GUARD> a{};
+  static_cast<SgdHyper&>(a) = u.h;
+  a.sched_advance = a.sched && a.sched_advance ? 1 : 0;
+  if constexpr (LARS) static_cast<LarsArgs&>(a) = u.lars;
+  if constexpr (GUARD) static_cast<ClipArgs&>(a) = u.clip;
+  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD>), dim3(u.n_items), dim3(256), 0, st, u.items,
+                     u.descs, u.p, u.g, u.buf, a);
+  return (int)hipGetLastError();
+}
+
+template <bool WITH_P, class Partial>
+static int launch_chunk_sums(const void* items, int n_items, const float* p, const float* g,
+                             float grad_scale, Partial* partial, hipStream_t st) {
+  if (n_items <= 0) return 0;
+  ChunkSumArgs<WITH_P> a{};
+  if constexpr (WITH_P) a.p = p;
+  a.items = (const int4*)items; a.g = g; a.grad_scale = grad_scale; a.partial = partial;
+  hipLaunchKernelGGL(chunk_sums_kernel<WITH_P>, dim3(n_items), dim3(256), 0, st, a);
+  return (int)hipGetLastError();
 }
 
 }  // namespace ddp_amd
@@ -765,58 +665,23 @@ extern "C" int ddp_pack_conv_weights(const PackDesc* descs, int n, hipStream_t s
   return (int)hipGetLastError();
 }
 
-extern "C" int ddp_sgd_pack(const void* items, int n_items, const long long* descs, float* p,
-                            float* g, float* buf, float lr, float momentum, float wd,
-                            float grad_scale, int nesterov, int zero_grad, int* counter,
-                            int delta, const unsigned* skip, unsigned short* shadow, float* slot,
-                            unsigned* done, unsigned* signal, LrSched* sched, int sched_advance,
-                            const void* lars_side, const void* lars_tensors,
-                            const void* lars_partial, float* lars_trust, float lars_eta,
-                            float lars_eps, const float* clip_partial, int clip_chunks,
-                            float clip_max_norm, float clip_eps, int clip_flags,
-                            float* clip_stats, hipStream_t st) {
-  SgdHyper h{lr, momentum, wd, grad_scale, nesterov, zero_grad, counter, delta, skip, shadow, slot,
-             done, signal, sched, sched && sched_advance ? 1 : 0};
-  if (n_items <= 0) return 0;
-  if (clip_partial && (!clip_stats || clip_chunks < 0)) return -1;
-  ClipArgs ca{clip_partial, clip_chunks, clip_max_norm, clip_eps, clip_flags, clip_stats};
-  if (lars_side) {
-    if (!lars_tensors || !lars_partial || !lars_trust) return -1;
-    LarsArgs la{(const int2*)lars_side, (const int4*)lars_tensors, (const float2*)lars_partial,
-                lars_trust, lars_eta, lars_eps};
-    if (clip_partial) {
-      hipLaunchKernelGGL(lars_clip_pack_kernel, dim3(n_items), dim3(256), 0, st,
-                         (const int4*)items, descs, p, g, buf, h, la, ca);
-      return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(lars_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items,
-                       descs, p, g, buf, h, la);
-    return (int)hipGetLastError();
-  }
-  if (clip_partial) {
-    hipLaunchKernelGGL(sgd_clip_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items,
-                       descs, p, g, buf, h, ca);
-    return (int)hipGetLastError();
-  }
-  hipLaunchKernelGGL(sgd_pack_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, descs,
-                     p, g, buf, h);
-  return (int)hipGetLastError();
+extern "C" int ddp_sgd_pack(const UpdateLaunch* u, hipStream_t st) {
+  if (u->n_items <= 0) return 0;
+  const bool lars = u->lars.side, guard = u->clip.partial;
+  if (guard && (!u->clip.stats || u->clip.n_chunks < 0)) return -1;
+  if (lars && (!u->lars.tensors || !u->lars.partial || !u->lars.trust)) return -1;
+  return (lars ? (guard ? launch_update<true, true> : launch_update<true, false>)
+               : (guard ? launch_update<false, true> : launch_update<false, false>))(*u, st);
 }
 
 extern "C" int ddp_grad_sumsq(const void* items, int n_items, const float* g, float grad_scale,
                               float* partial, hipStream_t st) {
-  if (n_items <= 0) return 0;
-  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, g,
-                     grad_scale, partial);
-  return (int)hipGetLastError();
+  return launch_chunk_sums<false>(items, n_items, nullptr, g, grad_scale, partial, st);
 }
 
 extern "C" int ddp_lars_norms(const void* items, int n_items, const float* p, const float* g,
                               float grad_scale, void* partial, hipStream_t st) {
-  if (n_items <= 0) return 0;
-  hipLaunchKernelGGL(lars_norms_kernel, dim3(n_items), dim3(256), 0, st, (const int4*)items, p, g,
-                     grad_scale, (float2*)partial);
-  return (int)hipGetLastError();
+  return launch_chunk_sums<true>(items, n_items, p, g, grad_scale, (float2*)partial, st);
 }
 
 extern "C" int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,
@@ -831,12 +696,8 @@ extern "C" int ddp_shard_tail(const void* segs, int n_segs, const float* src, fl
   return (int)hipGetLastError();
 }
 
-// Host-side tile shape (must match tile_dims above) so Python can build the item table.
-extern "C" void ddp_sgd_tile_dims(int RS, int* TK, int* TC) {
-  if (RS == 1) { *TK = 64; *TC = 64; }
-  else if (RS <= 9) { *TK = 32; *TC = 32; }
-  else { *TK = 8; *TC = 16; }
-}
+// Host-side tile shape so Python can build the item table.
+extern "C" void ddp_sgd_tile_dims(int RS, int* TK, int* TC) { tile_dims(RS, TK, TC); }
 
 // Floats of the tile kernel's LDS tile: a tile item needs TK * TC * R * S of them, and the
 // Python table builder refuses a tensor that needs more.

@@ -16,13 +16,13 @@ every tensor. Conv masters are stored [K][R][S][C] on the GPU: a norm does not d
 element order.
 
 GPU: two launches per update launch of FusedSGD, both captured with the step
-(csrc/kernels/optim.hip): ``lars_norms_kernel`` writes one {sum p^2, sum (g gs)^2} partial per
-8192-element chunk of every adapted tensor in the range, into the slot of the chunk's number in
-the WHOLE arena (per-bucket launches on the comm stream never share a slot), and the LARS
-instantiation of the fused SGD + re-pack kernel sums its tensor's partials in a fixed order in
-every block's prologue. No float atomics, no host sync: the result is reproducible and does not
-depend on the launch's parameter range. The partial and ratio buffers are allocated once, so
-their addresses survive re-captures.
+(csrc/kernels/optim.hip): ``chunk_sums_kernel<true>`` writes one {sum p^2, sum (g gs)^2} partial
+per 8192-element chunk of every adapted tensor in the range, into the slot of the chunk's number
+in the WHOLE arena (per-bucket launches on the comm stream never share a slot), and the LARS
+instantiation of ``sgd_pack_kernel`` (the fused SGD + re-pack) sums its tensor's partials in a
+fixed order in every block's prologue. No float atomics, no host sync: the result is
+reproducible and does not depend on the launch's parameter range. The partial and ratio buffers
+are allocated once, so their addresses survive re-captures.
 
 What LARS cannot do: an update that runs before the whole gradient exists (SGD in the backward)
 or that sees only a shard of a tensor (ZeRO-1, the bf16-gather sharded update) has no norm to
@@ -91,18 +91,11 @@ class LARS(FusedSGD):
         return self._lars_tensors
 
     def _norm_table(self, rng):
-        """Work items of the norms launch over parameters [i0, i1): one per chunk of every
-        adapted tensor, {arena offset, count, global chunk number, -}."""
-        t = self._norm_tables.get(rng)
-        if t is None:
-            a, ad = self.arena, self._adapted()
-            rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c, 0]
-                    for i in range(*rng) if ad[i]
-                    for c, s0 in enumerate(range(0, a.numels[i], self.CHUNK))]
-            t = (torch.tensor(rows, dtype=torch.int32, device=a.data.device) if rows else None,
-                 len(rows))
-            self._norm_tables[rng] = t
-        return t
+        """Work items of the norms launch over parameters [i0, i1): FusedSGD._chunk_table over
+        the adapted tensors; cached per range."""
+        if rng not in self._norm_tables:
+            self._norm_tables[rng] = self._chunk_table(rng, self._adapted())
+        return self._norm_tables[rng]
 
     def _side_table(self, key):
         """Side table parallel to the work-item table ``key`` of FusedSGD._work_table: per item

@@ -2,8 +2,8 @@
 
 Reference parity: ``optim.SGD(params, lr=0.1, momentum=0.9, weight_decay=1e-4)``
 (part1/main.py:124-125, part3/main.py:176-177): no dampening, no nesterov, momentum buffer
-initialised to the first gradient. On the GPU one launch of ``sgd_kernel`` (csrc/kernels/optim.hip)
-updates the whole flat parameter arena, followed by one launch that re-packs every conv weight
+initialised to the first gradient. On the GPU one launch of ``sgd_pack_kernel``
+(csrc/kernels/optim.hip) updates the whole flat parameter arena and re-packs every conv weight
 into the bf16 MFMA operand layouts the next forward consumes. On the CPU it is exactly
 ``torch.optim.SGD`` (the oracle).
 
@@ -28,9 +28,9 @@ fp32) changes no master, no momentum and no bf16 operand copy; it still clears t
 counted (``skipped_steps()``). Without ``skip_nonfinite`` a non-finite norm gives c = 0 or NaN
 as the arithmetic says. The captured step has no place between ``backward()`` and ``step()``
 where ``clip_grad_norm_`` could stand, so on the GPU the guard lives in the update launch
-(csrc/kernels/optim.hip): ``grad_sumsq_kernel`` stores one partial sum per 8192-element chunk,
-and the clipped instantiation of the fused update sums all of them in a fixed order in every
-block's prologue — no float atomics, no host sync, nothing baked in at capture. An optimizer
+(csrc/kernels/optim.hip): ``chunk_sums_kernel<false>`` stores one partial sum per 8192-element
+chunk, and the guarded instantiation of ``sgd_pack_kernel`` sums all of them in a fixed order in
+every block's prologue — no float atomics, no host sync, nothing baked in at capture. An optimizer
 with the guard needs the whole gradient before any element moves: no SGD in the backward, no
 sharded update (after a reduce-scatter a rank holds a shard of the gradient only, and the
 global norm would need one more collective); ``update="allreduce"`` is the plan to use. On the
@@ -84,6 +84,7 @@ class FusedSGD(torch.optim.SGD):
         self._lr_step = 0    # host mirror of the device step word: steps taken so far
         self._lr_dev = None  # device LrSched: int32 [step, n, next, pad] + n fp32 rates
         self._guard_dev = None
+        self._elem_tables = {}
         self._guard_cpu = [float("nan"), 1.0, 0]  # norm, coefficient, skipped steps
         self._set_guard(max_grad_norm, clip_eps, skip_nonfinite)
 
@@ -101,7 +102,7 @@ class FusedSGD(torch.optim.SGD):
         self._grad_scale_factor = float(v)
 
     # ------------------------------------------------------------------------ gradient guard
-    CHUNK = 8192  # elements per sum-of-squares block (optim.hip kNormChunk; the items' chunking)
+    CHUNK = 8192  # elements per elementwise item and per chunk-sum block (optim.hip kNormChunk)
 
     def _set_guard(self, max_grad_norm, clip_eps, skip_nonfinite):
         """Set the guard's options (constructor, load_state_dict). They live in
@@ -159,19 +160,22 @@ class FusedSGD(torch.optim.SGD):
             return self._guard_dev.view(torch.int32)[2]
         return torch.tensor(self._guard_cpu[2], dtype=torch.int32)
 
+    def _chunk_table(self, rng, keep=None):
+        """Work items of a chunk-sum launch (the guard's sum of squares, LARS' norms) over
+        parameters [i0, i1), those with ``keep[i]`` if given: one per chunk, {arena offset,
+        count, global chunk number, -}. Returns (device table or None, rows)."""
+        a = self.arena
+        rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c, 0]
+                for i in range(*rng) if keep is None or keep[i]
+                for c, s0 in enumerate(range(0, a.numels[i], self.CHUNK))]
+        return (torch.tensor(rows, dtype=torch.int32, device=a.data.device) if rows else None,
+                len(rows))
+
     def _sumsq_table(self, rng):
-        """Work items of the sum-of-squares launch over parameters [i0, i1): one per chunk,
-        {arena offset, count, global chunk number, -}; cached per range."""
-        t = self._sumsq_tables.get(rng)
-        if t is None:
-            a = self.arena
-            rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c, 0]
-                    for i in range(*rng)
-                    for c, s0 in enumerate(range(0, a.numels[i], self.CHUNK))]
-            t = (torch.tensor(rows, dtype=torch.int32, device=a.data.device) if rows else None,
-                 len(rows))
-            self._sumsq_tables[rng] = t
-        return t
+        """``_chunk_table`` over every parameter of the range; cached per range."""
+        if rng not in self._sumsq_tables:
+            self._sumsq_tables[rng] = self._chunk_table(rng)
+        return self._sumsq_tables[rng]
 
     def grad_sumsq(self, params=None, stream=None):
         """Launch the sum-of-squares pass over parameters ``params = (i0, i1)`` (default: all)
@@ -406,8 +410,8 @@ class FusedSGD(torch.optim.SGD):
                 n = a.numels[i]
                 if not wt and C == Cr and (krsc or R * S == 1) and n % 4 == 0:
                     # bf16 copy in the master's own index order: elementwise items
-                    for s0 in range(0, n, 8192):
-                        per_param[i].append([2, s0, min(8192, n - s0), d])
+                    for s0 in range(0, n, self.CHUNK):
+                        per_param[i].append([2, s0, min(self.CHUNK, n - s0), d])
                     continue
                 TK, TC = native().sgd_tile_dims(R * S)
                 if TK * TC * R * S > native().sgd_tile_limit():
@@ -419,13 +423,12 @@ class FusedSGD(torch.optim.SGD):
                 for k0 in range(0, K, TK):
                     for c0 in range(0, C, TC):
                         per_param[i].append([1, d, k0, c0])
-            chunk = 8192
             for i in range(len(a.params)):
                 if per_param[i]:
                     continue
                 o, n = a.offsets[i], a.numels[i]
-                for s in range(0, n, chunk):
-                    per_param[i].append([0, o + s, min(chunk, n - s), 0])
+                for s in range(0, n, self.CHUNK):
+                    per_param[i].append([0, o + s, min(self.CHUNK, n - s), 0])
             self._per_param = per_param
             dev = a.data.device
             self._descs = torch.tensor(descs if descs else [[0] * 12], dtype=torch.int64, device=dev)
@@ -454,16 +457,13 @@ class FusedSGD(torch.optim.SGD):
     def _elem_table(self, lo, hi):
         """Plain fp32 SGD items over arena elements [lo, hi) (no bf16 re-pack): the ZeRO-1
         shard update (parallel/zero.py)."""
-        key = ("elems", lo, hi)
-        t = getattr(self, "_elem_tables", {}).get(key)
+        t = self._elem_tables.get((lo, hi))
         if t is None:
-            chunk = 8192
-            items = [[0, s0, min(chunk, hi - s0), 0] for s0 in range(lo, hi, chunk)]
+            items = [[0, s0, min(self.CHUNK, hi - s0), 0] for s0 in range(lo, hi, self.CHUNK)]
             if not items:
                 raise ValueError("empty element range")
             t = (torch.tensor(items, dtype=torch.int32, device=self.arena.data.device), len(items))
-            self._elem_tables = getattr(self, "_elem_tables", {})
-            self._elem_tables[key] = t
+            self._elem_tables[(lo, hi)] = t
         return t
 
     @torch.no_grad()

@@ -21,6 +21,8 @@ it per bucket on the comm stream. CPU (Gloo): the same sequence with torch.distr
 """
 import torch
 
+from ..optim.sgd import FusedSGD
+
 
 class ShardedUpdate:
     def __init__(self, arena, optimizer, comm, buckets):
@@ -311,8 +313,8 @@ class ShardedBf16Update:
         items = []
         mine = {s: k for s, _, k in plan["small"][rank]}
         for s, e, op in self._pieces(s0, s1):
-            for c0 in range(s, e, 8192):
-                c1 = min(e, c0 + 8192)
+            for c0 in range(s, e, FusedSGD.CHUNK):
+                c1 = min(e, c0 + FusedSGD.CHUNK)
                 items.append([3, c0, c1 - c0, -1 if op else mine[s] + (c0 - s)])
         for a0, a1 in ((lo, s0), (s1, hi)):
             for c0 in range(a0, a1, 65536):

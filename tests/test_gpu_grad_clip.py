@@ -1,5 +1,5 @@
 """Gradient clipping and non-finite step skipping on the GPU (optim/sgd.py, optim/lars.py;
-csrc/kernels/optim.hip grad_sumsq_kernel + sgd_clip_pack_kernel / lars_clip_pack_kernel): norm,
+csrc/kernels/optim.hip chunk_sums_kernel<false> + sgd_pack_kernel<., true>): norm,
 coefficient and verdict are computed on the device by every launch, eager and replayed."""
 import pytest
 import torch
@@ -12,7 +12,7 @@ DEV = "cuda"
 
 # Longest serial chain of rounded additions behind the sum of squares of the whole gradient (all
 # terms are non-negative, so a chain of k additions is off by at most k * 2^-24 relative):
-#   grad_sumsq_kernel      8 float4 iterations x 4 fmas + 1 tail fma per thread        33
+#   chunk_sums_kernel      8 float4 iterations x 4 fmas + 1 tail fma per thread        33
 #                          wave_sum: 4 DPP levels + 2 levels over the four rows          6
 #                          four wave results added serially by thread 0                 3
 #   clipped update launch  lane l adds chunks l, l + 64, ... (14 chunks here: one each)   1

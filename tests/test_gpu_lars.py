@@ -1,5 +1,6 @@
-"""LARS on the GPU (optim/lars.py, csrc/kernels/optim.hip lars_norms_kernel + lars_pack_kernel):
-per-tensor trust ratios computed on the device by every launch, eager and replayed."""
+"""LARS on the GPU (optim/lars.py, csrc/kernels/optim.hip chunk_sums_kernel<true> +
+sgd_pack_kernel<true, .>): per-tensor trust ratios computed on the device by every launch, eager
+and replayed."""
 import pytest
 import torch
 
@@ -9,10 +10,10 @@ ETA, EPS, WD, MOM, GS = 0.02, 1e-8, 1e-4, 0.9, 0.5
 
 # Longest serial chain of rounded additions behind one tensor's sum of squares (all terms are
 # non-negative, so a chain of k additions is off by at most k * 2^-24 relative):
-#   lars_norms_kernel   8 float4 iterations x 4 fmas + 1 tail fma per thread        33
+#   chunk_sums_kernel   8 float4 iterations x 4 fmas + 1 tail fma per thread        33
 #                       wave_sum: 4 DPP levels + 2 levels over the four rows          6
 #                       four wave results added serially by thread 0                 3
-#   lars_pack_kernel    lane l adds chunks l, l + 64, ... (<= 64 chunks here)          1
+#   sgd_pack_kernel     lane l adds chunks l, l + 64, ... (<= 64 chunks here)          1
 #                       wave_sum                                                     6
 CHAIN = 33 + 6 + 3 + 1 + 6
 # trust = eta * wn / (gn + wd * wn + eps): the square roots halve each norm's error (CHAIN / 2

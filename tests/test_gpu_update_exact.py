@@ -152,10 +152,12 @@ def launch(nat, items, rows, A, h, lr_arg=None, **kw):
 
 
 def check_launch(nat, items, rows, A, h, steps, mem=None, shadow=None, slot=None, check_ties=False,
-                 osched=None, **kw):
+                 osched=None, ohyper=None, guard_skipped=False, **kw):
     """``steps`` launches of one table, each compared with the oracle: p, g, buf, every bf16 copy,
     shadow and slot, whole buffers. ``osched``: the oracle's image of the schedule the launch
-    reads. Returns the last oracle state."""
+    reads. ``ohyper``: the oracle's hyper-parameters where the launch's own guard changes them
+    (grad_scale * c); ``guard_skipped``: the oracle runs the guard's skipped step (exact mode).
+    Returns the last oracle state."""
     mem = mem or {}
     o = None
     for step in range(steps):
@@ -171,7 +173,8 @@ def check_launch(nat, items, rows, A, h, steps, mem=None, shadow=None, slot=None
         launch(nat, items, rows, A, h, shadow=shadow.ptr if shadow else 0,
                slot=slot.ptr if slot else 0, **kw)
         if A.exact:
-            o = uo.run_items(items, rows, p, g, buf, h, exact=True, **okw)
+            o = uo.run_items(items, rows, p, g, buf, ohyper or h, exact=True,
+                             guard_skipped=guard_skipped, **okw)
             same_bits(A.p.host(), A.p.expect(before["p"], f32_of(o["p"])), f"step {step}: p")
             same_bits(A.buf.host(), A.buf.expect(before["buf"], f32_of(o["buf"])),
                       f"step {step}: buf")
@@ -444,51 +447,130 @@ def mixed_table():
     return [items[i] for i in order], rows, off + 64, soff + 8
 
 
+class MixedCase:
+    """mixed_table() on the device: arena, bf16 copies (prefilled and poisoned), shadow, slot,
+    control words {counter, done ticket, signal, -} and a schedule at step 1 of 3. The kernel gets
+    lr = 99 as its immediate argument: with a schedule attached it must read the table's entry
+    of step 1, as the oracle does."""
+
+    def __init__(self, nat, exact, zero_grad=1):
+        self.items, self.rows, n, nslot = mixed_table()
+        assert len(self.items) >= 300 and {it[0] for it in self.items} == {0, 1, 2, 3, 4, 5}
+        self.A = Arena(n, 51, exact)
+        self.mem = {}
+        for r in self.rows:
+            wc = Buf(r[6], torch.bfloat16)
+            wt = Buf(r[7], torch.bfloat16) if r[7] else None
+            r[6], r[7] = wc.ptr, wt.ptr if wt else 0
+            prefill(nat, self.A, r, wc, wt)
+            self.mem[wc.ptr] = wc
+            if wt:
+                self.mem[wt.ptr] = wt
+        self.shadow = Buf(n, torch.bfloat16)
+        self.slot = Buf(nslot, fill=torch.full((nslot,), -3.0))
+        self.ctl = Buf(4, torch.int32, fill=torch.tensor([10, 0, 7, 0], dtype=torch.int32))
+        ptr, self.cb = self.ctl.ptr, self.ctl.host()
+        self.sched = lr_sched([0.5, 2.0 ** -2 if exact else 0.1, 0.125], 1)
+        self.h = dict(EXACT if exact else PROJECT, nesterov=0, zero_grad=zero_grad, delta=3,
+                      sched_advance=1)
+        self.h["lr"] = uo.f32(self.h["lr"])
+        self.kw = dict(counter=ptr, done=ptr + 4, signal=ptr + 8, sched=self.sched.data_ptr())
+        self.osched = dict(step=1, n=3, next=1, rates=[0.5, self.h["lr"], 0.125])
+        self.launches = 0
+
+    def check(self, nat, steps, **kw):
+        """``steps`` launches through check_launch, then the control words: the ticket reset by
+        every launch, the counter and the signal raised, next == step + 1 (nothing commits it)."""
+        o = check_launch(nat, self.items, self.rows, self.A, self.h, steps, mem=self.mem,
+                         shadow=self.shadow, slot=self.slot, osched=self.osched, lr_arg=99.0,
+                         **self.kw, **kw)
+        self.launches += steps
+        self.check_control("control")
+        return o
+
+    def check_control(self, what):
+        want = [10 + 3 * self.launches, 0, 7 + self.launches, 0]
+        same_bits(self.ctl.host(), self.ctl.expect(self.cb, torch.tensor(want, dtype=torch.int32)),
+                  what)
+        assert self.sched[:4].tolist() == [1, 3, 2, 0]
+
+    def check_skip_word(self, nat, extra=None, **kw):
+        """Skip word set: nothing but the counter, the signal and the staged step may change
+        (``extra``: further buffers that must stay as they are)."""
+        skip = torch.ones(1, dtype=torch.int32, device=DEV)
+        self.A.new_grad(9)
+        bufs = dict(p=self.A.p, g=self.A.g, buf=self.A.buf, shadow=self.shadow, slot=self.slot,
+                    **{str(k): b for k, b in self.mem.items()}, **(extra or {}))
+        before = {k: b.host() for k, b in bufs.items()}
+        self.sched[2] = 1
+        launch(nat, self.items, self.rows, self.A, self.h, lr_arg=99.0, shadow=self.shadow.ptr,
+               slot=self.slot.ptr, skip=skip.data_ptr(), **self.kw, **kw)
+        self.launches += 1
+        for k, b in bufs.items():
+            same_bits(b.host(), before[k], f"skipped launch: {k}")
+        self.check_control("control after the skipped launch")
+
+
 @pytest.mark.parametrize("exact", [True, False])
 def test_mixed_table(native_ext, exact):
-    items, rows, n, nslot = mixed_table()
-    assert len(items) >= 300 and {it[0] for it in items} == {0, 1, 2, 3, 4, 5}
-    A = Arena(n, 51, exact)
-    mem = {}
-    for r in rows:
-        wc = Buf(r[6], torch.bfloat16)
-        wt = Buf(r[7], torch.bfloat16) if r[7] else None
-        r[6], r[7] = wc.ptr, wt.ptr if wt else 0
-        prefill(native_ext, A, r, wc, wt)
-        mem[wc.ptr] = wc
-        if wt:
-            mem[wt.ptr] = wt
-    shadow, slot = Buf(n, torch.bfloat16), Buf(nslot, fill=torch.full((nslot,), -3.0))
-    ctl = Buf(4, torch.int32, fill=torch.tensor([10, 0, 7, 0], dtype=torch.int32))
-    ptr, cb = ctl.ptr, ctl.host()
-    sched = lr_sched([0.5, 2.0 ** -2 if exact else 0.1, 0.125], 1)
-    h = dict(EXACT if exact else PROJECT, nesterov=0, zero_grad=1, delta=3, sched_advance=1)
-    h["lr"] = uo.f32(h["lr"])
-    kw = dict(counter=ptr, done=ptr + 4, signal=ptr + 8, sched=sched.data_ptr())
-    steps = 2 if exact else 1
-    # the kernel gets lr = 99 as its immediate argument: with a schedule attached it must read
-    # the table's entry of step 1, as the oracle does
-    osched = dict(step=1, n=3, next=1, rates=[0.5, h["lr"], 0.125])
-    check_launch(native_ext, items, rows, A, h, steps, mem=mem, shadow=shadow, slot=slot,
-                 check_ties=exact, osched=osched, lr_arg=99.0, **kw)
-    want = [10 + 3 * steps, 0, 7 + steps, 0]   # ticket reset by every launch, signal raised
-    same_bits(ctl.host(), ctl.expect(cb, torch.tensor(want, dtype=torch.int32)), "control")
-    assert sched[:4].tolist() == [1, 3, 2, 0]   # next == step + 1 (nothing commits it here)
-    # skip word set: nothing but the counter, the signal and the staged step may change
-    skip = torch.ones(1, dtype=torch.int32, device=DEV)
-    A.new_grad(9)
-    bufs = dict(p=A.p, g=A.g, buf=A.buf, shadow=shadow, slot=slot,
-                **{str(k): b for k, b in mem.items()})
-    before = {k: b.host() for k, b in bufs.items()}
-    sched[2] = 1
-    launch(native_ext, items, rows, A, h, lr_arg=99.0, shadow=shadow.ptr, slot=slot.ptr,
-           skip=skip.data_ptr(), **kw)
-    for k, b in bufs.items():
-        same_bits(b.host(), before[k], f"skipped launch: {k}")
-    want = [10 + 3 * (steps + 1), 0, 7 + steps + 1, 0]
-    same_bits(ctl.host(), ctl.expect(cb, torch.tensor(want, dtype=torch.int32)),
-              "control after the skipped launch")
-    assert sched[:4].tolist() == [1, 3, 2, 0]
+    m = MixedCase(native_ext, exact)
+    m.check(native_ext, 2 if exact else 1, check_ties=exact)
+    m.check_skip_word(native_ext)
+
+
+def guard_buffers(partials, skipped=5):
+    """The guard's device inputs: per-chunk partial sums and the statistics words {norm, c,
+    skipped steps, -} (as int32 bit patterns), both between guard bands."""
+    part = Buf(len(partials), fill=torch.tensor(partials))
+    stats = Buf(4, torch.int32, fill=torch.tensor([0x11111111, 0x22222222, skipped, 0x44444444],
+                                                  dtype=torch.int32))
+    return part, stats
+
+
+def f32_bits(x):
+    return int(np.array([x], np.float32).view(np.int32)[0])
+
+
+@pytest.mark.parametrize("zero_grad", [0, 1], ids=["zero_grad=0", "zero_grad=1"])
+def test_mixed_table_guard_skipped(native_ext, zero_grad):
+    """A non-finite norm with skip_nonfinite (clip flag 2) through the raw table: items 0-3 only
+    clear their gradient range (with zero_grad), exactly the range the update covers -- whole
+    guarded buffers against the oracle; items 4 and 5, the counter, the signal and the staged
+    step as in any step; the statistics hold norm = +inf and c (1.0 without the clip flag,
+    2 / (inf + eps) = 0.0 with it) and the skipped count goes up by one."""
+    m = MixedCase(native_ext, True, zero_grad)
+    part, stats = guard_buffers([1.0, float("inf"), 1.0])
+    pb, sb = part.host(), stats.host()
+    ckw = dict(clip_partial=part.ptr, clip_chunks=3, clip_max_norm=2.0, clip_eps=1e-6,
+               clip_stats=stats.ptr)
+    count = 5
+    for flags in ((2 | 4, 1 | 2 | 4) if zero_grad else (2 | 4,)):
+        m.A.new_grad(20 + flags)
+        m.check(native_ext, 1, guard_skipped=True, clip_flags=flags, **ckw)
+        count += 1
+        want = [f32_bits(float("inf")), f32_bits(0.0 if flags & 1 else 1.0), count, 0x44444444]
+        same_bits(stats.host(), stats.expect(sb, torch.tensor(want, dtype=torch.int32)),
+                  f"statistics, flags {flags}")
+        same_bits(part.host(), pb, "partials")
+    # the skip word keeps precedence: nothing is touched and nothing recorded
+    stats.set(torch.tensor([0x11111111, 0x22222222, count, 0x44444444], dtype=torch.int32))
+    m.check_skip_word(native_ext, extra=dict(stats=stats, partials=part), clip_flags=2 | 4, **ckw)
+
+
+def test_mixed_table_clip_half(native_ext):
+    """Partials {4, 0, 12}: norm = sqrt(16) = 4, c = 2 / (4 + 0) = 0.5, all exact. One exact-mode
+    step must equal the oracle's unguarded run with grad_scale 2**-1 * 0.5 = 2**-2 (the oracle
+    asserts that every intermediate is an fp32 number); the statistics hold {4.0, 0.5} and the
+    skipped count stays."""
+    m = MixedCase(native_ext, True)
+    part, stats = guard_buffers([4.0, 0.0, 12.0])
+    pb, sb = part.host(), stats.host()
+    m.check(native_ext, 1, ohyper=dict(m.h, grad_scale=2.0 ** -2),
+            clip_partial=part.ptr, clip_chunks=3, clip_max_norm=2.0, clip_eps=0.0,
+            clip_flags=1 | 2 | 4, clip_stats=stats.ptr)
+    want = [f32_bits(4.0), f32_bits(0.5), 5, 0x44444444]
+    same_bits(stats.host(), stats.expect(sb, torch.tensor(want, dtype=torch.int32)), "statistics")
+    same_bits(part.host(), pb, "partials")
 
 
 # ------------------------------------------------------------------------------ pack_conv_weights

@@ -130,6 +130,45 @@ def test_run_items_rules():
     assert bool((t["p"] >= o["p"].abs()).all()) and bool((t["buf"] >= o["buf"].abs()).all())
 
 
+@pytest.mark.parametrize("krsc", [0, 1])
+def test_run_items_guard_skipped(krsc):
+    """A guard-skipped launch: items 0-3 change nothing but g, which becomes +0 exactly where the
+    normal launch with zero_grad clears it (and nowhere without zero_grad); items 4 and 5 run;
+    counter, signal and staged step as in any step; the skip word keeps precedence."""
+    K, Cr, C, R = 40, 3, 8, 3   # two tiles along K, channel padded
+    n = 2048
+    p, g, buf = _recipe(n, 70)
+    g[g == 0] = 1.0   # every cleared element is then visible
+    d = [64, K, Cr, C, R, R, 1001, 1002, krsc, 0, 0, 0]
+    d2 = [1280, 4, 4, 4, 1, 1, 1003, 0, 0, 0, 0, 0]
+    mem = {1001: np.full(K * R * R * C, 0x7fc5, np.uint16),
+           1002: np.full(C * R * R * K, 0x7fc5, np.uint16), 1003: np.full(16, 0x7fc5, np.uint16)}
+    items = uo.tile_items(0, d)[:1] + [[0, 1200, 5, 0], [4, 1216, 8, 0], [3, 1232, 8, 4],
+                                       [2, 4, 8, 1], [5, 12, 4, 1]]
+    sched = dict(step=1, n=2, next=1, rates=[0.5, 0.25])
+    kw = dict(mem=mem, shadow=np.full(n, 0x7fc5, np.uint16), slot=torch.full((64,), -1.0).double(),
+              counter=10, done=0, signal=7, sched=sched)
+    for zg in (0, 1):
+        h = dict(EXACT, nesterov=0, zero_grad=zg, delta=3, sched_advance=1)
+        o = uo.run_items(items, [d, d2], p, g, buf, h, exact=True, **kw)
+        s = uo.run_items(items, [d, d2], p, g, buf, h, guard_skipped=True, **kw)
+        assert s["counter"] == 13 and s["done"] == 0 and s["signal"] == 8
+        assert s["sched"]["next"] == 2
+        assert torch.equal(s["p"], p) and torch.equal(s["buf"], buf)
+        assert (s["shadow"] == 0x7fc5).all() and bool((s["slot"] == -1.0).all())
+        assert all(np.array_equal(s["mem"][k], mem[k]) for k in (1001, 1002))
+        # item 5 ran (the old masters' bf16), item 2 did not write its copy
+        assert np.array_equal(s["mem"][1003][12:16], uo.bf16_bits_of(p[1292:1296]))
+        assert (s["mem"][1003][:12] == 0x7fc5).all()
+        # g: exactly what the normal launch leaves (item 4's range always, the rest with zero_grad)
+        assert torch.equal(s["g"], o["g"])
+        cleared = int((s["g"] == 0).sum())
+        assert cleared == (8 + zg * (32 * Cr * R * R + 5 + 8 + 8))
+        # the skip word keeps precedence
+        w = uo.run_items(items, [d, d2], p, g, buf, h, guard_skipped=True, skip=1, **kw)
+        assert torch.equal(w["g"], g) and np.array_equal(w["mem"][1003], mem[1003])
+
+
 # ---------------------------------------------------------------------- what the old checks miss
 def old_allclose(got, ref):
     return torch.allclose(got, ref, rtol=1e-5, atol=1e-6)

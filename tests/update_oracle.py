@@ -172,7 +172,7 @@ def lr_of(hyper, sched):
 
 def run_items(items, descs, p, g, buf, hyper, mem=None, shadow=None, slot=None, skip=0,
               counter=None, done=None, signal=None, sched=None, exact=False, pack_source=None,
-              abs_pass=False):
+              abs_pass=False, guard_skipped=False):
     """One fused launch. ``items``: rows of 4 ints; ``descs``: rows of 12 ints {p_offset, K, Cr,
     C, R, S, wc, wt, krsc, -, -, -} whose wc / wt entries are keys into ``mem`` (the device
     pointers on the GPU); ``hyper``: lr, momentum, wd, grad_scale, nesterov, zero_grad, delta,
@@ -188,7 +188,12 @@ def run_items(items, descs, p, g, buf, hyper, mem=None, shadow=None, slot=None, 
     desc}: bf16 copy only. zero_grad writes +0. counter += delta even when skipped; a non-zero
     skip word leaves p, g, buf, every bf16 copy, shadow and slot unchanged; with a signal, done is
     0 afterwards and the signal one higher, skipped or not; with a schedule and sched_advance,
-    next == step + 1, skipped or not."""
+    next == step + 1, skipped or not.
+
+    ``guard_skipped``: the gradient guard found a non-finite norm (optim.hip ClipArgs flag 2).
+    Items 0-3 then change nothing but g, which becomes +0 over exactly the range the update
+    covers, and only with zero_grad; items 4 and 5 run as always; counter, signal and staged
+    step as in any step. The skip word keeps precedence."""
     h = hyper
     out = dict(p=p.double().clone(), g=g.double().clone(), buf=buf.double().clone(),
                mem={k: v.copy() for k, v in (mem or {}).items()},
@@ -222,7 +227,18 @@ def run_items(items, descs, p, g, buf, hyper, mem=None, shadow=None, slot=None, 
 
     for it in items:
         kind, a, b_, c = (int(v) for v in it)
-        if kind in (0, 3):
+        if guard_skipped and kind in (0, 1, 2, 3):
+            if not h.get("zero_grad"):
+                continue
+            if kind == 1:
+                d = descs[a]
+                TK, TC = tile_dims(int(d[4]) * int(d[5]))
+                c1r = max(c, min(int(d[2]), c + TC))
+                _master_view(G, d)[b_:min(int(d[1]), b_ + TK), :, :, c:c1r] = 0.0
+            else:
+                lo = a + (int(descs[c][0]) if kind == 2 else 0)
+                G[lo:lo + b_] = 0.0
+        elif kind in (0, 3):
             sl = slice(a, a + b_)
             np_, nb = upd(P[sl], G[sl], B[sl])
             P[sl], B[sl] = np_, nb

@@ -21,6 +21,7 @@ import argparse
 import csv
 import json
 import os
+import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,16 +30,19 @@ ARMS = ("sgd_nobwd", "clip_never", "clip_always")
 # (the synthetic set is memorised within a few hundred steps and the gradient norm falls by
 # orders of magnitude: "always" has to stay below any norm the run can reach)
 NEVER, ALWAYS = 1e30, 1e-12
+# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD>, and the sum-of-squares launch
+UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false)>")
+SUMSQ = "chunk_sums_kernel<false>"
 
 
 def summarise(prefix):
     trace = sorted(csv.DictReader(open(prefix + "_kernel_trace.csv")),
                    key=lambda r: int(r["Start_Timestamp"]))
-    idx = [i for i, r in enumerate(trace) if "pack_kernel" in r["Kernel_Name"]
-           and "pack_conv" not in r["Kernel_Name"]]
+    idx = [i for i, r in enumerate(trace) if UPDATE.search(r["Kernel_Name"])]
     runs = []  # [update kernel, dispatches per step, consecutive steps]
     for a, b in zip(idx[:-1], idx[1:]):
-        name = "sgd_clip_pack" if "clip" in trace[b]["Kernel_Name"] else "sgd_pack"
+        guard = UPDATE.search(trace[b]["Kernel_Name"]).group(2) == "true"
+        name = "sgd_clip_pack" if guard else "sgd_pack"
         if runs and runs[-1][0] == name and runs[-1][1] == b - a:
             runs[-1][2] += 1
         else:
@@ -47,7 +51,7 @@ def summarise(prefix):
     for name, n, k in runs:
         if k >= 5:
             print(f"  {name}: {n} x {k}")
-    for key in ("grad_sumsq", "sgd_clip_pack", "sgd_pack_kernel"):
+    for key in (SUMSQ, "sgd_pack_kernel<false, true>", "sgd_pack_kernel<false, false>"):
         rows = [r for r in trace if key in r["Kernel_Name"]]
         if rows:
             us = sorted((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows)

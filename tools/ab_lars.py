@@ -19,21 +19,25 @@ import argparse
 import csv
 import json
 import os
+import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ARMS = ("sgd", "sgd_nobwd", "lars")
+# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD>, and the norms launch
+UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false)>")
+NORMS = "chunk_sums_kernel<true>"
 
 
 def summarise(prefix):
     trace = sorted(csv.DictReader(open(prefix + "_kernel_trace.csv")),
                    key=lambda r: int(r["Start_Timestamp"]))
-    idx = [i for i, r in enumerate(trace) if "pack_kernel" in r["Kernel_Name"]
-           and "pack_conv" not in r["Kernel_Name"]]
+    idx = [i for i, r in enumerate(trace) if UPDATE.search(r["Kernel_Name"])]
     runs = []  # [update kernel, dispatches per step, consecutive steps]
     for a, b in zip(idx[:-1], idx[1:]):
-        name = "lars_pack" if "lars" in trace[b]["Kernel_Name"] else "sgd_pack"
+        lars = UPDATE.search(trace[b]["Kernel_Name"]).group(1) == "true"
+        name = "lars_pack" if lars else "sgd_pack"
         if runs and runs[-1][0] == name and runs[-1][1] == b - a:
             runs[-1][2] += 1
         else:
@@ -42,17 +46,17 @@ def summarise(prefix):
     for name, n, k in runs:
         if k >= 5:
             print(f"  {name}: {n} x {k}")
-    norms = [r for r in trace if "lars_norms" in r["Kernel_Name"]]
+    norms = [r for r in trace if NORMS in r["Kernel_Name"]]
     if norms:
         us = sorted((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in norms)
         wg = int(norms[-1]["Workgroup_Size_X"]) or 1
         blocks = int(norms[-1]["Grid_Size_X"]) // wg
-        print(f"lars_norms_kernel: {len(us)} launches, {blocks} blocks, median {us[len(us) // 2]:.2f} us, "
+        print(f"{NORMS}: {len(us)} launches, {blocks} blocks, median {us[len(us) // 2]:.2f} us, "
               f"min {us[0]:.2f} us")
     stats = prefix + "_kernel_stats.csv"
     if os.path.exists(stats):
         for r in csv.DictReader(open(stats)):
-            if "lars" in r["Name"] or "sgd_pack" in r["Name"]:
+            if NORMS in r["Name"] or "sgd_pack" in r["Name"]:
                 print(f"  stats: {r['Name'][:60]} calls {r['Calls']} avg {float(r['AverageNs']) / 1e3:.2f} us")
 
 
