@@ -77,6 +77,14 @@ static const ddp_amd::BnBwdApply* bn_apply(py::object o, ddp_amd::BnBwdApply* ou
   return out;
 }
 
+// (smoothing, partner labels | 0, lam | 0)
+static ddp_amd::SoftTarget soft_target(py::object o) {
+  auto t = o.cast<py::tuple>();
+  if (t.size() != 3) throw std::runtime_error("soft target needs (smoothing, labels_b, lam)");
+  return {t[0].cast<float>(), P<long long>(t[1].cast<uintptr_t>()),
+          P<float>(t[2].cast<uintptr_t>())};
+}
+
 static ddp_amd::ConvGeom geom(py::tuple g) {
   if (g.size() != 12 && g.size() != 13) throw std::runtime_error("conv geometry needs 12/13 ints");
   ddp_amd::ConvGeom c;
@@ -477,30 +485,47 @@ PYBIND11_MODULE(_native, m) {
   m.def("bn_bwd_local_set", [](long long max_loads) { ddp_bn_bwd_local_set(max_loads); });
   m.def("conv_epi_stage_set", [](int on) { ddp_conv_epi_stage_set(on); });
 
+  // ``soft`` (here and in the two loss entry points below): None = the plain kernel, else
+  // (smoothing, partner-label pointer | 0, lam pointer | 0) = api.h SoftTarget
   m.def("linear_ce_fwd", [](uintptr_t x, uintptr_t W, uintptr_t b, uintptr_t labels, int B, int F,
                             int J, uintptr_t logits, uintptr_t dlogits, uintptr_t loss_sum,
-                            uintptr_t correct, uintptr_t st, uintptr_t loss_acc) {
+                            uintptr_t correct, uintptr_t st, uintptr_t loss_acc, py::object soft) {
+    if (!soft.is_none()) {
+      const ddp_amd::SoftTarget s = soft_target(soft);
+      check(ddp_linear_ce_fwd_soft(nullptr, P<void>(x), P<float>(W), P<float>(b),
+                                   P<long long>(labels), B, F, J, P<float>(logits),
+                                   P<float>(dlogits), P<float>(loss_sum), P<int>(correct),
+                                   P<float>(loss_acc), &s, S(st)), "linear_ce_fwd (soft)");
+      return;
+    }
     check(ddp_linear_ce_fwd(P<void>(x), P<float>(W), P<float>(b), P<long long>(labels), B, F, J,
                             P<float>(logits), P<float>(dlogits), P<float>(loss_sum),
                             P<int>(correct), P<float>(loss_acc), S(st)), "linear_ce_fwd");
   }, py::arg("x"), py::arg("W"), py::arg("b"), py::arg("labels"), py::arg("B"), py::arg("F"),
      py::arg("J"), py::arg("logits"), py::arg("dlogits"), py::arg("loss_sum"), py::arg("correct"),
-     py::arg("stream"), py::arg("loss_acc") = 0);
+     py::arg("stream"), py::arg("loss_acc") = 0, py::arg("soft") = py::none());
   // the head with the last block's BN + ReLU + 2x2 pool folded in (writes the features y)
   m.def("bn_pool_linear_ce_fwd", [](uintptr_t z, uintptr_t stats, uintptr_t gamma, uintptr_t beta,
                                     float eps, int relu, uintptr_t coef, uintptr_t y, uintptr_t W,
                                     uintptr_t b, uintptr_t labels, int B, int F, int J,
                                     uintptr_t dlogits, uintptr_t loss_sum, uintptr_t st,
-                                    uintptr_t loss_acc) {
+                                    uintptr_t loss_acc, py::object soft) {
     ddp_amd::HeadBnIn h{P<unsigned short>(z), P<float>(stats), P<float>(gamma), P<float>(beta),
                         eps, relu, P<float>(coef), P<unsigned short>(y)};
+    if (!soft.is_none()) {
+      const ddp_amd::SoftTarget s = soft_target(soft);
+      check(ddp_linear_ce_fwd_soft(&h, nullptr, P<float>(W), P<float>(b), P<long long>(labels), B,
+                                   F, J, nullptr, P<float>(dlogits), P<float>(loss_sum), nullptr,
+                                   P<float>(loss_acc), &s, S(st)), "bn_pool_linear_ce_fwd (soft)");
+      return;
+    }
     check(ddp_bn_pool_linear_ce_fwd(&h, P<float>(W), P<float>(b), P<long long>(labels), B, F, J,
                                     P<float>(dlogits), P<float>(loss_sum), nullptr,
                                     P<float>(loss_acc), S(st)), "bn_pool_linear_ce_fwd");
   }, py::arg("z"), py::arg("stats"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
      py::arg("relu"), py::arg("coef"), py::arg("y"), py::arg("W"), py::arg("b"), py::arg("labels"),
      py::arg("B"), py::arg("F"), py::arg("J"), py::arg("dlogits"), py::arg("loss_sum"),
-     py::arg("stream"), py::arg("loss_acc") = 0);
+     py::arg("stream"), py::arg("loss_acc") = 0, py::arg("soft") = py::none());
   m.def("linear_bwd", [](uintptr_t dlogits, uintptr_t x, uintptr_t W, int B, int F, int J,
                          uintptr_t gscale, uintptr_t dx, uintptr_t dW, uintptr_t db,
                          uintptr_t st) {
@@ -509,10 +534,19 @@ PYBIND11_MODULE(_native, m) {
   });
   m.def("softmax_ce", [](uintptr_t logits, int bf16, uintptr_t labels, int B, int J,
                          uintptr_t loss_sum, uintptr_t correct, uintptr_t dlogits,
-                         int dlogits_bf16, uintptr_t st) {
+                         int dlogits_bf16, uintptr_t st, py::object soft) {
+    if (!soft.is_none()) {
+      const ddp_amd::SoftTarget s = soft_target(soft);
+      check(ddp_softmax_ce_soft(P<void>(logits), bf16, P<long long>(labels), B, J,
+                                P<float>(loss_sum), P<int>(correct), P<void>(dlogits),
+                                dlogits_bf16, &s, S(st)), "softmax_ce (soft)");
+      return;
+    }
     check(ddp_softmax_ce(P<void>(logits), bf16, P<long long>(labels), B, J, P<float>(loss_sum),
                          P<int>(correct), P<void>(dlogits), dlogits_bf16, S(st)), "softmax_ce");
-  });
+  }, py::arg("logits"), py::arg("bf16"), py::arg("labels"), py::arg("B"), py::arg("J"),
+     py::arg("loss_sum"), py::arg("correct"), py::arg("dlogits"), py::arg("dlogits_bf16"),
+     py::arg("stream"), py::arg("soft") = py::none());
 
   m.def("sgd", [](uintptr_t p, uintptr_t g, uintptr_t buf, size_t n, float lr, float momentum,
                   float wd, float grad_scale, int nesterov, uintptr_t st, uintptr_t sched) {
@@ -625,7 +659,7 @@ PYBIND11_MODULE(_native, m) {
                       int L, int B, int H, int W, int Cp, int pad, int flip, unsigned int seed,
                       unsigned int epoch, std::vector<float> mean, std::vector<float> std_,
                       uintptr_t x, uintptr_t y, uintptr_t st, uintptr_t zero, size_t zero_n,
-                      uintptr_t sched, int cursor_off) {
+                      uintptr_t sched, int cursor_off, py::object mix) {
     ddp_amd::AugArgs a{};
     a.cursor_off = cursor_off;
     a.sched = P<ddp_amd::LrSched>(sched);
@@ -636,12 +670,21 @@ PYBIND11_MODULE(_native, m) {
     a.flip = flip; a.seed = seed; a.epoch = epoch;
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean.at(c); a.inv_std[c] = 1.f / std_.at(c); }
     a.x = P<unsigned short>(x); a.y = P<long long>(y);
+    if (!mix.is_none()) {  // mixup: (y2, lam table, entries, lam_cur) = api.h MixArgs
+      auto t = mix.cast<py::tuple>();
+      if (t.size() != 4) throw std::runtime_error("mix needs (y2, table, n, lam_cur)");
+      const ddp_amd::MixArgs mx{P<long long>(t[0].cast<uintptr_t>()),
+                                P<float>(t[1].cast<uintptr_t>()), t[2].cast<int>(),
+                                P<float>(t[3].cast<uintptr_t>())};
+      check(ddp_augment_mix(&a, &mx, S(st)), "augment (mixup)");
+      return;
+    }
     check(ddp_augment(&a, S(st)), "augment");
   }, py::arg("images"), py::arg("labels"), py::arg("indices"), py::arg("cursor"), py::arg("L"),
      py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cp"), py::arg("pad"), py::arg("flip"),
      py::arg("seed"), py::arg("epoch"), py::arg("mean"), py::arg("std"), py::arg("x"),
      py::arg("y"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0,
-     py::arg("sched") = 0, py::arg("cursor_off") = 0);
+     py::arg("sched") = 0, py::arg("cursor_off") = 0, py::arg("mix") = py::none());
   m.def("nchw_to_nhwc", [](uintptr_t x, int N, int C, int H, int W, int Cp, uintptr_t out,
                            uintptr_t st) {
     check(ddp_nchw_to_nhwc(P<float>(x), N, C, H, W, Cp, P<void>(out), S(st)), "nchw_to_nhwc");

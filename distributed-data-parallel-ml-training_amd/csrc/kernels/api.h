@@ -307,6 +307,26 @@ struct AugArgs {
                                 //   becomes current (LrSched: step = next) before this step's updates
 };
 
+// Mixup in the batch launch (data.hip augment_kernel<true>; AugArgs itself does not grow): sample
+// b is blended with sample B-1-b of the same batch, lam = table[(cursor + cursor_off) % n] (the
+// host's per-epoch Beta(alpha, alpha) draws, data/loader.py lam_table; read through the cursor
+// so that a captured step mixes every replay with its own entry).
+struct MixArgs {
+  long long* y2;       // [B] the partner's labels (written)
+  const float* table;  // [n] mixing weights of the epoch, one per loader batch
+  int n;
+  float* lam_cur;      // one float (written): this batch's weight, where the loss kernel reads it
+};
+
+// Soft targets of the loss kernels (linear_ce.hip, the SOFT instantiations only):
+// t_j = (1 - smoothing) * (lam * [j == ya] + (1 - lam) * [j == yb]) + smoothing / J, ya = the
+// ``labels`` argument. ``lam`` is a device pointer because a captured graph bakes scalars in.
+struct SoftTarget {
+  float smoothing;            // label smoothing E, 0 <= E < 1
+  const long long* labels_b;  // [B] mixup partner labels yb (null: yb = ya)
+  const float* lam;           // one float, the batch's mixing weight (null: 1)
+};
+
 }  // namespace ddp_amd
 
 extern "C" {
@@ -382,6 +402,15 @@ int ddp_linear_bwd(const float* dlogits, const void* x, const float* W, int B, i
 int ddp_softmax_ce(const void* logits, int logits_bf16, const long long* labels, int B, int J,
                    float* loss_sum, int* correct, void* dlogits, int dlogits_bf16,
                    hipStream_t st);
+// the three loss launchers over soft targets (SoftTarget; labels are required); bn == null: the
+// plain head on ``x``, else the head with the last block folded in
+int ddp_linear_ce_fwd_soft(const ddp_amd::HeadBnIn* bn, const void* x, const float* W,
+                           const float* b, const long long* labels, int B, int F, int J,
+                           float* logits, float* dlogits, float* loss_sum, int* correct,
+                           float* loss_acc, const ddp_amd::SoftTarget* soft, hipStream_t st);
+int ddp_softmax_ce_soft(const void* logits, int logits_bf16, const long long* labels, int B, int J,
+                        float* loss_sum, int* correct, void* dlogits, int dlogits_bf16,
+                        const ddp_amd::SoftTarget* soft, hipStream_t st);
 // sched (optional, here and below): device learning-rate table used instead of ``lr``
 int ddp_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd,
             float grad_scale, int nesterov, const ddp_amd::LrSched* sched, hipStream_t st);
@@ -453,7 +482,9 @@ int ddp_sgd_tile_limit();  // floats of the LDS tile: a tile item needs TK * TC 
 int ddp_counter_add(int* c, int delta, ddp_amd::LrSched* sched, int sched_mode, hipStream_t st);
 int ddp_synth_generate(unsigned char* images, int* labels, int n, int pix_per_img,
                        unsigned int seed, int classes, hipStream_t st);
+// ddp_augment_mix: the mixup instantiation (MixArgs); -1 when one of its pointers is missing
 int ddp_augment(const ddp_amd::AugArgs* a, hipStream_t st);
+int ddp_augment_mix(const ddp_amd::AugArgs* a, const ddp_amd::MixArgs* mix, hipStream_t st);
 int ddp_nchw_to_nhwc(const float* x, int N, int C, int H, int W, int Cp, void* out,
                      hipStream_t st);
 int ddp_maxpool_fwd(const void* x, int N, int H, int W, int C, int KH, int KW, int stride,

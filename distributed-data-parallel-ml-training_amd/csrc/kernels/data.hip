@@ -41,33 +41,62 @@ __global__ __launch_bounds__(256) void synth_generate_kernel(unsigned char* imag
   }
 }
 
-__global__ __launch_bounds__(256) void augment_kernel(AugArgs a) {
+__device__ __forceinline__ const MixArgs& only(const MixArgs& m) { return m; }
+
+// MIX (mixup, ``mix`` = one MixArgs; the plain instantiation takes AugArgs alone): sample b is
+// blended in fp32 with sample B-1-b of the same batch, each under its own crop / flip, by the
+// batch's weight lam = table[(cursor + cursor_off) % n]; y2 receives the partner's label and
+// one thread publishes lam for the loss kernel.
+template <bool MIX, class... Mix>
+__global__ __launch_bounds__(256) void augment_kernel(AugArgs a, Mix... mix) {
+  static_assert(sizeof...(Mix) == (MIX ? 1 : 0), "MixArgs goes to the mixed instantiation only");
+  constexpr int kSrc = MIX ? 2 : 1;
   const int cur = a.cursor ? *a.cursor : 0;
+  [[maybe_unused]] float lam = 1.f;
+  if constexpr (MIX) {
+    const MixArgs& m = only(mix...);
+    lam = m.table[(int)(((long long)cur + a.cursor_off) % m.n)];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *m.lam_cur = lam;
+  }
   const size_t total = (size_t)a.B * a.H * a.W;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += stride) {
     const int b = (int)(t / ((size_t)a.H * a.W));
     const int pix = (int)(t % ((size_t)a.H * a.W));
     const int oy = pix / a.W, ox = pix % a.W;
-    const int pos = (int)(((long long)(cur + a.cursor_off) * a.B + b) % a.L);
-    const int idx = a.indices[pos];
-    int cy = 0, cx = 0, fl = 0;
-    if (a.pad > 0 || a.flip) {
-      const uint32_t h = hash3(a.seed ^ 0x68e31da4u, a.epoch, (uint32_t)idx);
-      const int span = 2 * a.pad + 1;
-      cy = (int)(h % span);
-      cx = (int)((h / span) % span);
-      fl = a.flip ? (int)((h >> 20) & 1u) : 0;
-    }
-    const int sx = fl ? (a.W - 1 - ox) : ox;            // flip after crop
-    const int iy = oy + cy - a.pad, ix = sx + cx - a.pad;  // zero padding outside the image
     u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    const bool in = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-    const unsigned char* src = a.images + (((size_t)idx * a.H + (in ? iy : 0)) * a.W + (in ? ix : 0)) * 3;
+    float px[kSrc][3];  // MIX: the fp32 pixels of the sample [0] and of its partner [1]
+    int idxs[kSrc];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float raw = in ? (float)src[c] : 0.f;
-      v[c] = f2bf((raw * (1.f / 255.f) - a.mean[c]) * a.inv_std[c]);
+    for (int s = 0; s < kSrc; ++s) {
+      const int bs = s ? a.B - 1 - b : b;
+      const int pos = (int)(((long long)(cur + a.cursor_off) * a.B + bs) % a.L);
+      const int idx = a.indices[pos];
+      idxs[s] = idx;
+      int cy = 0, cx = 0, fl = 0;
+      if (a.pad > 0 || a.flip) {
+        const uint32_t h = hash3(a.seed ^ 0x68e31da4u, a.epoch, (uint32_t)idx);
+        const int span = 2 * a.pad + 1;
+        cy = (int)(h % span);
+        cx = (int)((h / span) % span);
+        fl = a.flip ? (int)((h >> 20) & 1u) : 0;
+      }
+      const int sx = fl ? (a.W - 1 - ox) : ox;            // flip after crop
+      const int iy = oy + cy - a.pad, ix = sx + cx - a.pad;  // zero padding outside the image
+      const bool in = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+      const unsigned char* src = a.images + (((size_t)idx * a.H + (in ? iy : 0)) * a.W + (in ? ix : 0)) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float raw = in ? (float)src[c] : 0.f;
+        px[s][c] = (raw * (1.f / 255.f) - a.mean[c]) * a.inv_std[c];
+        if constexpr (!MIX) v[c] = f2bf(px[s][c]);
+      }
+    }
+    const int idx = idxs[0];
+    if constexpr (MIX) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = f2bf(lam * px[0][c] + (1.f - lam) * px[1][c]);
+      if (pix == 0) only(mix...).y2[b] = a.labels[idxs[1]];
     }
     unsigned short* dst = a.x + (size_t)t * a.Cp;
     if (a.Cp == 8) {
@@ -119,7 +148,17 @@ extern "C" int ddp_augment(const AugArgs* args, hipStream_t st) {
   AugArgs a = *args;
   size_t blocks = ((size_t)a.B * a.H * a.W + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(augment_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(augment_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ddp_augment_mix(const AugArgs* args, const MixArgs* mix, hipStream_t st) {
+  if (!mix || !mix->y2 || !mix->table || mix->n < 1 || !mix->lam_cur) return -1;
+  AugArgs a = *args;
+  size_t blocks = ((size_t)a.B * a.H * a.W + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL((augment_kernel<true, MixArgs>), dim3((unsigned)blocks), dim3(256), 0, st, a,
+                     *mix);
   return (int)hipGetLastError();
 }
 

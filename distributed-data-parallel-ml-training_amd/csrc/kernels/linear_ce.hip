@@ -26,11 +26,41 @@ namespace ddp_amd {
 // of the four window pixels, max-pools them (bn_act.hip's rule) and stores the bf16 feature,
 // which then feeds the dot products exactly as a loaded x would.
 constexpr int kMaxHeadF = 1024;
-template <bool BN>
+
+// Soft targets (api.h SoftTarget; label smoothing E and mixup partner yb with weight lam) of one
+// row, as the SOFT instantiations of both loss kernels evaluate them:
+//   t_j       = fma(1 - E, wa [j == ya] + wb [j == yb], E / J)
+//   loss term = fma(E / J, sum_j z_j, (1 - E) * fma(wa, z_ya, wb * z_yb))
+// with (wa, wb) = (lam, 1 - lam), or (1, 0) when yb == ya (lam + (1 - lam) is 1 without a
+// rounding). E = 0, lam = 1 or yb == ya gives t = onehot(ya) and the term z_ya, bit for bit.
+struct SoftRow {
+  float om, u, wa, wb;  // 1 - E, E / J, the two label weights
+  int yb;
+  __device__ __forceinline__ SoftRow(const SoftTarget& s, int row, int ya, int J) {
+    const float lam = s.lam ? *s.lam : 1.f;
+    yb = s.labels_b ? (int)s.labels_b[row] : ya;
+    om = 1.f - s.smoothing;
+    u = s.smoothing / (float)J;
+    wa = yb == ya ? 1.f : lam;
+    wb = yb == ya ? 0.f : 1.f - lam;
+  }
+  __device__ __forceinline__ float target(int j, int ya) const {
+    return __builtin_fmaf(om, (j == ya ? wa : 0.f) + (j == yb ? wb : 0.f), u);
+  }
+  __device__ __forceinline__ float term(float z_ya, float z_yb, float sum_z) const {
+    return __builtin_fmaf(u, sum_z, om * __builtin_fmaf(wa, z_ya, wb * z_yb));
+  }
+};
+__device__ __forceinline__ const SoftTarget& only(const SoftTarget& s) { return s; }
+
+// SOFT: ``soft`` = one SoftTarget, passed to the soft instantiations only (the plain ones keep
+// their argument list); everything soft sits under ``if constexpr (SOFT)``.
+template <bool BN, bool SOFT, class... Soft>
 __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(
     const unsigned short* __restrict__ x, const float* __restrict__ W, const float* __restrict__ b,
     const long long* __restrict__ labels, int B, int F, int J, float inv_b, float* logits_out,
-    float* dlogits, float* loss_sum, int* correct, float* loss_acc, HeadBnIn bn) {
+    float* dlogits, float* loss_sum, int* correct, float* loss_acc, HeadBnIn bn, Soft... soft) {
+  static_assert(sizeof...(Soft) == (SOFT ? 1 : 0), "SoftTarget goes to the soft instantiations");
   __shared__ float cf[BN ? 2 * kMaxHeadF : 1];
   if constexpr (BN) {
     const float M = 4.f * B;
@@ -121,7 +151,9 @@ __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(
     if (logits_out) logits_out[(size_t)row * J + lane] = lj;
     if (dlogits && labels) {
       const float p = __expf(lj - lse);
-      dlogits[(size_t)row * J + lane] = (p - (lane == y ? 1.f : 0.f)) * inv_b;
+      float t = lane == y ? 1.f : 0.f;
+      if constexpr (SOFT) t = SoftRow(only(soft...), row, y, J).target(lane, y);
+      dlogits[(size_t)row * J + lane] = (p - t) * inv_b;
     }
   }
   // per-block reduction of the 4 rows' loss / hit terms, then one atomic per accumulator
@@ -132,6 +164,18 @@ __global__ __launch_bounds__(256) void linear_ce_fwd_kernel(
 #pragma unroll
     for (int j = 0; j < kMaxJ; ++j)
       if (j == y) ly = acc[j];
+    if constexpr (SOFT) {
+      if (labels) {
+        const SoftRow sr(only(soft...), row, y, J);
+        float lyb = 0.f, sz = 0.f;
+#pragma unroll
+        for (int j = 0; j < kMaxJ; ++j) {
+          if (j == sr.yb) lyb = acc[j];
+          if (j < J) sz += acc[j];
+        }
+        ly = sr.term(ly, lyb, sz);
+      }
+    }
     lrow[threadIdx.x >> 6] = (live && labels) ? (lse - ly) * inv_b : 0.f;
     hrow[threadIdx.x >> 6] = (live && labels && arg == y) ? 1 : 0;
   }
@@ -193,12 +237,15 @@ __global__ __launch_bounds__(256) void linear_bwd_kernel(const float* __restrict
 
 // Generic softmax cross-entropy on [B][J] logits (bf16 or fp32), one block per row.
 // Writes dlogits (bf16, scaled by 1/B * g) for the MFMA GEMM backward.
+// SOFT (one SoftTarget, as in the head): one more block reduction, the sum of the row's logits.
+template <bool SOFT, class... Soft>
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const void* logits, int logits_bf16,
                                                          const long long* labels, int B, int J,
                                                          float inv_b, float* loss_sum,
                                                          int* correct, void* dlogits,
-                                                         int dlogits_bf16) {
-  __shared__ float red[2][4];
+                                                         int dlogits_bf16, Soft... soft) {
+  static_assert(sizeof...(Soft) == (SOFT ? 1 : 0), "SoftTarget goes to the soft instantiation");
+  __shared__ float red[SOFT ? 3 : 2][4];
   __shared__ int redi[4];
   const int row = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -226,21 +273,38 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const void* logits, int
   float se = 0.f;
   for (int j = tid; j < J; j += 256) se += __expf(get(j) - mx);
   se = wave_sum(se);
+  float sz = 0.f;
+  if constexpr (SOFT) {
+    for (int j = tid; j < J; j += 256) sz += get(j);
+    sz = wave_sum(sz);
+  }
   __syncthreads();
-  if (lane == 0) red[1][wid] = se;
+  if (lane == 0) {
+    red[1][wid] = se;
+    if constexpr (SOFT) red[2][wid] = sz;
+  }
   __syncthreads();
   se = red[1][0] + red[1][1] + red[1][2] + red[1][3];
   const float lse = mx + __logf(se);
   const int y = (int)labels[row];
+  auto target = [&](int j) -> float {
+    if constexpr (SOFT) return SoftRow(only(soft...), row, y, J).target(j, y);
+    else return j == y ? 1.f : 0.f;
+  };
   if (dlogits)
     for (int j = tid; j < J; j += 256) {
       const float p = __expf(get(j) - lse);
-      const float d = (p - (j == y ? 1.f : 0.f)) * inv_b;
+      const float d = (p - target(j)) * inv_b;
       if (dlogits_bf16) ((unsigned short*)dlogits)[(size_t)row * J + j] = f2bf(d);
       else ((float*)dlogits)[(size_t)row * J + j] = d;
     }
   if (tid == 0) {
-    if (loss_sum) atomicAdd(loss_sum, (lse - get(y)) * inv_b);
+    float ly = get(y);
+    if constexpr (SOFT) {
+      const SoftRow sr(only(soft...), row, y, J);
+      ly = sr.term(ly, get(sr.yb), red[2][0] + red[2][1] + red[2][2] + red[2][3]);
+    }
+    if (loss_sum) atomicAdd(loss_sum, (lse - ly) * inv_b);
     if (correct && arg == y) atomicAdd(correct, 1);
   }
 }
@@ -254,7 +318,7 @@ extern "C" int ddp_linear_ce_fwd(const void* x, const float* W, const float* b,
                                  float* dlogits, float* loss_sum, int* correct, float* loss_acc,
                                  hipStream_t st) {
   if (J > kMaxJ || F % 8) return -1;
-  hipLaunchKernelGGL(linear_ce_fwd_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, st,
+  hipLaunchKernelGGL((linear_ce_fwd_kernel<false, false>), dim3((B + 3) / 4), dim3(256), 0, st,
                      (const unsigned short*)x, W, b, labels, B, F, J, 1.f / (float)B, logits,
                      dlogits, loss_sum, correct, loss_acc, HeadBnIn{});
   return (int)hipGetLastError();
@@ -268,9 +332,34 @@ extern "C" int ddp_bn_pool_linear_ce_fwd(const HeadBnIn* bn, const float* W, con
   if (J > kMaxJ || F % 8 || F > kMaxHeadF || !bn || !bn->z || !bn->stats || !bn->gamma ||
       !bn->beta || !bn->coef || !bn->y)
     return -1;
-  hipLaunchKernelGGL(linear_ce_fwd_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, st,
+  hipLaunchKernelGGL((linear_ce_fwd_kernel<true, false>), dim3((B + 3) / 4), dim3(256), 0, st,
                      (const unsigned short*)bn->y, W, b, labels, B, F, J, 1.f / (float)B,
                      nullptr, dlogits, loss_sum, correct, loss_acc, *bn);
+  return (int)hipGetLastError();
+}
+
+// labels must be valid class indices for every row: yb addresses a lane's logits like ya
+static bool soft_ok(const SoftTarget* s, const long long* labels) {
+  return s && labels && s->smoothing >= 0.f && s->smoothing < 1.f;
+}
+
+extern "C" int ddp_linear_ce_fwd_soft(const HeadBnIn* bn, const void* x, const float* W,
+                                      const float* b, const long long* labels, int B, int F, int J,
+                                      float* logits, float* dlogits, float* loss_sum, int* correct,
+                                      float* loss_acc, const SoftTarget* soft, hipStream_t st) {
+  if (J > kMaxJ || F % 8 || !soft_ok(soft, labels)) return -1;
+  if (bn) {
+    if (F > kMaxHeadF || !bn->z || !bn->stats || !bn->gamma || !bn->beta || !bn->coef || !bn->y)
+      return -1;
+    hipLaunchKernelGGL((linear_ce_fwd_kernel<true, true, SoftTarget>), dim3((B + 3) / 4),
+                       dim3(256), 0, st, (const unsigned short*)bn->y, W, b, labels, B, F, J,
+                       1.f / (float)B, nullptr, dlogits, loss_sum, correct, loss_acc, *bn, *soft);
+  } else {
+    hipLaunchKernelGGL((linear_ce_fwd_kernel<false, true, SoftTarget>), dim3((B + 3) / 4),
+                       dim3(256), 0, st, (const unsigned short*)x, W, b, labels, B, F, J,
+                       1.f / (float)B, logits, dlogits, loss_sum, correct, loss_acc, HeadBnIn{},
+                       *soft);
+  }
   return (int)hipGetLastError();
 }
 
@@ -289,7 +378,17 @@ extern "C" int ddp_linear_bwd(const float* dlogits, const void* x, const float* 
 extern "C" int ddp_softmax_ce(const void* logits, int logits_bf16, const long long* labels, int B,
                               int J, float* loss_sum, int* correct, void* dlogits,
                               int dlogits_bf16, hipStream_t st) {
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3(B), dim3(256), 0, st, logits, logits_bf16, labels, B,
-                     J, 1.f / (float)B, loss_sum, correct, dlogits, dlogits_bf16);
+  hipLaunchKernelGGL(softmax_ce_kernel<false>, dim3(B), dim3(256), 0, st, logits, logits_bf16,
+                     labels, B, J, 1.f / (float)B, loss_sum, correct, dlogits, dlogits_bf16);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ddp_softmax_ce_soft(const void* logits, int logits_bf16, const long long* labels,
+                                   int B, int J, float* loss_sum, int* correct, void* dlogits,
+                                   int dlogits_bf16, const SoftTarget* soft, hipStream_t st) {
+  if (!soft_ok(soft, labels)) return -1;
+  hipLaunchKernelGGL((softmax_ce_kernel<true, SoftTarget>), dim3(B), dim3(256), 0, st, logits,
+                     logits_bf16, labels, B, J, 1.f / (float)B, loss_sum, correct, dlogits,
+                     dlogits_bf16, *soft);
   return (int)hipGetLastError();
 }

@@ -27,6 +27,7 @@ from .synthetic import hash3
 CIFAR_MEAN = [x / 255.0 for x in [125.3, 123.0, 113.9]]
 CIFAR_STD = [x / 255.0 for x in [63.0, 62.1, 66.7]]
 AUG_SEED_XOR = 0x68e31da4
+MIX_SEED_TAG = 0x6d697875  # third word of the lam table's generator seed
 
 
 class _Len:
@@ -54,8 +55,31 @@ def crop_flip_params(seed, epoch, idx, pad=4, flip=True):
     return cy, cx, fl
 
 
-def augment_cpu(images, idx, seed, epoch, train=True, pad=4, mean=CIFAR_MEAN, std=CIFAR_STD):
-    """NCHW fp32 batch for sample indices ``idx`` (numpy twin of the HIP augment kernel)."""
+def lam_table(seed, epoch, alpha, n):
+    """Mixup weights of one epoch: ``n`` fp32 draws of Beta(alpha, alpha), one per loader batch,
+    a pure function of (dataset seed, epoch, alpha, n) — no rank in it, so replicas mix alike;
+    None when ``alpha`` is 0 (mixup off). Batch i of the epoch (micro-batch j of an accumulated
+    step: batch cursor + j) is mixed with entry i."""
+    if not alpha:
+        return None
+    rng = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(epoch), MIX_SEED_TAG])
+    return rng.beta(float(alpha), float(alpha), size=int(n)).astype(np.float32)
+
+
+def n_batches(n_samples, batch_size):
+    return math.ceil(n_samples / batch_size)
+
+
+def augment_cpu(images, idx, seed, epoch, train=True, pad=4, mean=CIFAR_MEAN, std=CIFAR_STD,
+                lam=None):
+    """NCHW fp32 batch for sample indices ``idx`` (numpy twin of the HIP augment kernel).
+    ``lam`` (mixup): sample b is blended in fp32 with sample B-1-b of the batch, each under its
+    own crop / flip, lam * a + (1 - lam) * b, and rounded to bf16-representable values like the
+    kernel's store."""
+    if lam is not None:
+        a = augment_cpu(images, idx, seed, epoch, train, pad, mean, std)
+        lam = torch.tensor(float(lam), dtype=torch.float32)
+        return (lam * a + (1 - lam) * a.flip(0)).to(torch.bfloat16).float()
     idx = np.asarray(idx)
     x = images[idx].astype(np.float32)  # [B, H, W, 3]
     B, H, W, _ = x.shape
@@ -75,15 +99,26 @@ def augment_cpu(images, idx, seed, epoch, train=True, pad=4, mean=CIFAR_MEAN, st
 
 class CPULoader:
     def __init__(self, dataset, batch_size, num_replicas=1, rank=0, train=True, shard=True,
-                 epoch=0, max_batches=None):
+                 epoch=0, max_batches=None, mixup_alpha=0.0):
         self.ds, self.batch_size, self.train = dataset, batch_size, train
         self.num_replicas = num_replicas if shard else 1
         self.rank = rank if shard else 0
-        self.epoch = epoch
         self.max_batches = max_batches
+        self.mixup_alpha = float(mixup_alpha)
+        self._soft = None
+        self.set_epoch(epoch)
 
     def set_epoch(self, e):
         self.epoch = e
+        self.lam_table = None
+        if self.mixup_alpha:
+            self.lam_table = lam_table(self.ds.seed, e, self.mixup_alpha,
+                                       n_batches(len(self.indices()), self.batch_size))
+
+    def soft_targets(self):
+        """Mixup on: (partner labels [B] int64, lam as a one-element fp32 tensor) of the batch
+        last produced; else None."""
+        return self._soft
 
     def indices(self):
         return shard_indices(len(self.ds), self.num_replicas, self.rank, epoch=self.epoch)
@@ -103,14 +138,22 @@ class CPULoader:
             if self.max_batches and bi >= self.max_batches:
                 break
             b = idx[s:s + self.batch_size]
-            yield augment_cpu(imgs, b, self.ds.seed, self.epoch, self.train), \
-                torch.from_numpy(labels[b].astype(np.int64))
+            y = torch.from_numpy(labels[b].astype(np.int64))
+            lam = None
+            if self.lam_table is not None:
+                lam = self.lam_table[bi]
+                self._soft = (y.flip(0), torch.tensor([float(lam)], dtype=torch.float32))
+            yield augment_cpu(imgs, b, self.ds.seed, self.epoch, self.train, lam=lam), y
 
 
 class DeviceLoader:
     def __init__(self, dataset, batch_size, device, num_replicas=1, rank=0, train=True,
-                 shard=True, epoch=0, max_batches=None, cpad=8):
+                 shard=True, epoch=0, max_batches=None, cpad=8, mixup_alpha=0.0):
         self.ds, self.batch_size, self.train = dataset, batch_size, train
+        # mixup (augment_kernel<MIX>): the epoch's lam table on the device, and for the static
+        # batch the partner labels and one lam slot per micro-batch offset of a step
+        self.mixup_alpha = float(mixup_alpha)
+        self.lam_table = self.lam_dev = self._soft = None
         self.device = torch.device(device)
         self.num_replicas = num_replicas if shard else 1
         self.rank = rank if shard else 0
@@ -134,12 +177,28 @@ class DeviceLoader:
         else:
             self.idx = idx.to(self.device)
         self.cursor.zero_()
+        if self.mixup_alpha:
+            self.lam_table = lam_table(self.ds.seed, e, self.mixup_alpha,
+                                       n_batches(idx.numel(), self.batch_size))
+            t = torch.from_numpy(self.lam_table)
+            if self.lam_dev is not None and self.lam_dev.numel() == t.numel():
+                self.lam_dev.copy_(t)  # in place, like the indices
+            else:
+                self.lam_dev = t.to(self.device)
+
+    MAX_MIX_OFFSETS = 64  # lam slots of the static batch: micro-batch offsets of one step
+
+    def soft_targets(self):
+        """Mixup on: (partner labels [B] int64, lam as a one-element fp32 tensor) of the batch
+        last launched, both written by that launch on the device (``fill``: the static partner
+        labels and the lam slot of the micro-batch offset); else None."""
+        return self._soft
 
     def __len__(self):
         n = math.ceil(self.idx.numel() / self.batch_size)
         return min(n, self.max_batches) if self.max_batches else n
 
-    def _launch(self, x, y, indices_ptr, L, B, cursor_ptr, sched=0, offset=0):
+    def _launch(self, x, y, indices_ptr, L, B, cursor_ptr, sched=0, offset=0, mix=None):
         from ..ops.common import native, stream_handle, step_scratch
         pad, flip = (4, 1) if self.train else (0, 0)
         # the augment launch also clears the per-step BN-statistics scratch that the next
@@ -151,14 +210,24 @@ class DeviceLoader:
                          self.ds.seed & 0xFFFFFFFF, self.epoch, CIFAR_MEAN, CIFAR_STD,
                          x.data_ptr(), y.data_ptr(), stream_handle(), zero=zp, zero_n=zn,
                          **({"sched": sched} if sched else {}),
-                         **({"cursor_off": int(offset)} if offset else {}))
+                         **({"cursor_off": int(offset)} if offset else {}),
+                         **({"mix": (mix[0].data_ptr(), self.lam_dev.data_ptr(),
+                                     self.lam_dev.numel(), mix[1].data_ptr())} if mix else {}))
+        self._soft = mix
 
     def batch(self, start, B):
-        """Materialise samples [start, start+B) of this rank's shard (new tensors)."""
+        """Materialise samples [start, start+B) of this rank's shard (new tensors). With mixup
+        the batch is loader batch ``start // batch_size`` of the epoch and takes that entry of
+        the lam table (the launch sees a shard of exactly these B samples, where the cursor
+        offset selects the entry and moves no sample)."""
         x = torch.empty(B, self.ds.height, self.ds.width, self.cpad, dtype=torch.bfloat16,
                         device=self.device)
         y = torch.empty(B, dtype=torch.int64, device=self.device)
-        self._launch(x, y, self.idx.data_ptr() + 4 * start, B, B, 0)
+        mix = None
+        if self.lam_dev is not None:
+            mix = (torch.empty_like(y), torch.empty(1, dtype=torch.float32, device=self.device))
+        self._launch(x, y, self.idx.data_ptr() + 4 * start, B, B, 0, mix=mix,
+                     offset=start // self.batch_size if mix else 0)
         return x, y
 
     def __iter__(self):
@@ -176,6 +245,10 @@ class DeviceLoader:
                             device=self.device)
             y = torch.empty(B, dtype=torch.int64, device=self.device)
             self._static = (x, y)
+            if self.lam_dev is not None:
+                self._static_mix = (torch.empty_like(y),
+                                    torch.zeros(self.MAX_MIX_OFFSETS, dtype=torch.float32,
+                                                device=self.device))
         return self._static
 
     def fill(self, advance=True, lr_sched=0, offset=0):
@@ -190,8 +263,14 @@ class DeviceLoader:
         advances by K)."""
         from ..ops.common import native, stream_handle
         x, y = self.static_batch()
+        mix = None
+        if self.lam_dev is not None:
+            if not 0 <= offset < self.MAX_MIX_OFFSETS:
+                raise ValueError(f"mixup: at most {self.MAX_MIX_OFFSETS} micro-batches per step")
+            y2, lams = self._static_mix
+            mix = (y2, lams[offset:offset + 1])
         self._launch(x, y, self.idx.data_ptr(), self.idx.numel(), self.batch_size,
-                     self.cursor.data_ptr(), sched=lr_sched, offset=offset)
+                     self.cursor.data_ptr(), sched=lr_sched, offset=offset, mix=mix)
         if advance:
             native().counter_add(self.cursor.data_ptr(), 1, stream_handle())
         return x, y
@@ -203,8 +282,9 @@ class DeviceLoader:
 
 
 def make_loader(dataset, batch_size, device, num_replicas=1, rank=0, train=True, shard=True,
-                max_batches=None):
+                max_batches=None, mixup_alpha=0.0):
     if torch.device(device).type == "cuda":
         return DeviceLoader(dataset, batch_size, device, num_replicas, rank, train, shard,
-                            max_batches=max_batches)
-    return CPULoader(dataset, batch_size, num_replicas, rank, train, shard, max_batches=max_batches)
+                            max_batches=max_batches, mixup_alpha=mixup_alpha)
+    return CPULoader(dataset, batch_size, num_replicas, rank, train, shard, max_batches=max_batches,
+                     mixup_alpha=mixup_alpha)

@@ -44,11 +44,12 @@ def main(part, argv=None):
     seed_everything(SEED)
     batch_size = int(args.global_batch / world)  # batch for one node
 
-    criterion = CrossEntropyLoss()
+    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)  # --label-smoothing
     train_ds = SyntheticCIFAR10(train=True, seed=SEED, n=args.train_size)
     test_ds = SyntheticCIFAR10(train=False, seed=SEED, n=args.test_size)
     train_loader = make_loader(train_ds, batch_size, device, world, rank, train=True,
-                               shard=distributed, max_batches=args.max_batches)
+                               shard=distributed, max_batches=args.max_batches,
+                               mixup_alpha=args.mixup_alpha)  # --mixup-alpha
     test_loader = make_loader(test_ds, batch_size, device, train=False, shard=False)
 
     model = build(args.model).to(device)

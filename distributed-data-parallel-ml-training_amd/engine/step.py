@@ -16,7 +16,7 @@ import torch
 
 from ..parallel.comm import is_live
 from ..utils.trace import trace_range
-from .trainer import grad_scaled, micro_batch_ctx
+from .trainer import batch_mix, grad_scaled, micro_batch_ctx
 
 
 def capture_mode():
@@ -75,6 +75,7 @@ class TrainStep:
         self.sync = sync
         self.use_graph = use_graph
         self.accum_steps = int(accum_steps)
+        self._lam_refs = self._graph_lams = []  # mixup: lam tensors of the last / captured step
         if self.accum_steps < 1:
             raise ValueError("accum_steps must be >= 1")
         dev = loader.device
@@ -112,15 +113,21 @@ class TrainStep:
         with micro_batch_ctx(self.model, j == 0, last), \
                 grad_scaled(self.optimizer, m if last else 1):
             with trace_range("data"):
-                x, y = batch if batch is not None else self.loader.fill(
-                    advance=not self.fold_opt, offset=j, **(self._lr_sched() if j == 0 else {}))
+                if batch is not None:
+                    x, y, mix = (*batch, None)[:3]
+                    if mix is not None:
+                        self._lam_refs.append(mix[1])
+                else:
+                    x, y = self.loader.fill(advance=not self.fold_opt, offset=j,
+                                            **(self._lr_sched() if j == 0 else {}))
+                    mix = self._mix()
             with trace_range("forward"):
                 if fwd is not None:
                     # classifier + loss + loss meter in one kernel (no logits tensor, no extra adds)
-                    loss = fwd(x, y, acc=self.loss_sum,
+                    loss = fwd(x, y, acc=self.loss_sum, **self._soft(mix),
                                **({"transient": True} if batch is None else {}))
                 else:
-                    loss = self.criterion(self.model(x), y)
+                    loss = self.criterion(self.model(x), y, *([mix] if mix else []))
             with trace_range("backward"):
                 loss.backward(self._one)  # persistent ones: no fill kernel for the seed gradient
             if last:
@@ -145,12 +152,32 @@ class TrainStep:
         """Micro-step j < K-1: batch cursor + j, forward, backward; no sync, no update."""
         self._micro(j, False)
 
+    def _soft(self, mix):
+        """``soft=`` of a fused forward + loss: the criterion's label smoothing and the batch's
+        mixup ``mix`` = (partner labels, lam) as one SoftTarget; nothing for the plain loss."""
+        soft = self.criterion.soft(mix) if hasattr(self.criterion, "soft") else None
+        return {"soft": soft} if soft is not None else {}
+
+    def _mix(self):
+        """(partner labels, lam) of the loader's batch just launched, or None; the lam tensor
+        (the static batch's: the slot every replay rewrites) is kept for ``lams``."""
+        mix = batch_mix(self.loader)
+        if mix is not None:
+            self._lam_refs.append(mix[1])
+        return mix
+
+    def lams(self):
+        """Mixup: the mixing weights of the last step's micro-batches, read from the device
+        (the values its batch launches published); [] without mixup. Synchronises."""
+        return [float(t) for t in self._lam_refs]
+
     def _run(self, m, batches=None):
         """One optimizer step over m micro-batches, every execution form: the loader's batches
         cursor .. cursor + m-1 (``_body``: eager, warm-up and what ``capture`` records), or the
         explicit ``batches`` (``tail_step``). SGD in the backward only with m == 1."""
         if m > 1 and not self.fold_opt:
             raise ValueError("an accumulated step needs the fused optimizer and the device loader")
+        self._lam_refs = []
         if batches is not None and self._lr_sched():
             # no batch launch of the loader precedes this step: make the learning-rate step
             # that the last replay staged current before the backward reads it
@@ -206,10 +233,12 @@ class TrainStep:
         with torch.cuda.graph(g, capture_error_mode=mode):
             self._body()
         self.graph = g
+        self._graph_lams = self._lam_refs  # the static lam slots the replays rewrite
 
     def step(self):
         if self.graph is not None:
             self.graph.replay()
+            self._lam_refs = self._graph_lams
             # a learning-rate schedule advances on the device inside the replay (optim/sgd.py
             # set_schedule); the optimizer's host mirror of the step index follows here
             if hasattr(self.optimizer, "count_step"):
@@ -488,15 +517,17 @@ class SegmentedDDPStep(TrainStep):
         if self.sync_buffers:
             self.ddp._sync_buffers()  # what DDP.forward would do (no-op without buffers / world 1)
         K = self.accum_steps
+        self._lam_refs = []
         with self.ddp.no_sync():
             for j in range(K - 1):  # accumulate-only micro-steps: whole, uncut, no collective
                 self._micro(j, False, forward_loss=self.ddp.module.forward_loss)
             with trace_range("data"):
                 x, y = self.loader.fill(advance=False, offset=K - 1,
                                         **(self._lr_sched() if K == 1 else {}))
+                mix = self._mix()
             with trace_range("forward"):
                 loss, cuts = self.ddp.module.forward_loss_split(
-                    x, y, self.split, acc=self.loss_sum, transient=True)
+                    x, y, self.split, acc=self.loss_sum, transient=True, **self._soft(mix))
             with trace_range("backward_seg0"):
                 loss.backward(self._one)
         self._cuts = cuts
@@ -631,6 +662,7 @@ class SegmentedDDPStep(TrainStep):
             graphs.append(g)
         self.graphs = graphs
         self.graph = graphs[0]  # "captured" marker for the shared helpers
+        self._graph_lams = self._lam_refs
 
     def step(self, seg_events=None):
         """One replayed step. ``seg_events``: list receiving a timing event recorded on the main
@@ -640,6 +672,7 @@ class SegmentedDDPStep(TrainStep):
             return
         if seg_events is not None:
             seg_events.append(self._probe_event(torch.cuda.current_stream()))
+        self._lam_refs = self._graph_lams
         for j, g in enumerate(self.graphs):
             g.replay()
             if seg_events is not None:

@@ -20,13 +20,38 @@ from ..utils.trace import trace_range
 
 
 class CrossEntropyLoss(nn.Module):
-    """``nn.CrossEntropyLoss()`` (mean); GPU logits use the fused softmax-CE HIP kernel."""
+    """``nn.CrossEntropyLoss()`` (mean); GPU logits use the fused softmax-CE HIP kernel.
+    ``label_smoothing`` = E as in torch (0: the reference's loss); ``mix`` = (partner labels,
+    lam) of a mixup batch (the loader's ``soft_targets()``): lam * CE(target) + (1 - lam) *
+    CE(partner). Both go through the soft-target form of the same kernels (``soft``)."""
 
-    def forward(self, logits, target):
+    def __init__(self, label_smoothing=0.0):
+        super().__init__()
+        e = float(label_smoothing)
+        if not 0.0 <= e < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        self.label_smoothing = e
+
+    def soft(self, mix=None):
+        """The SoftTarget of a batch (ops/common.py), or None for the plain one-hot loss."""
+        if not self.label_smoothing and mix is None:
+            return None
+        from ..ops.common import SoftTarget
+        return SoftTarget(self.label_smoothing, *(mix or (None, None)))
+
+    def forward(self, logits, target, mix=None):
+        soft = self.soft(mix)
         if logits.is_cuda:
             from ..ops.layers import cross_entropy
-            return cross_entropy(logits, target)
+            return cross_entropy(logits, target, soft)
+        if soft is not None:
+            return soft.torch_loss(logits, target)
         return nn.functional.cross_entropy(logits, target)
+
+
+def batch_mix(loader):
+    """(partner labels, lam) of the mixup batch a loader produced last, or None."""
+    return loader.soft_targets() if hasattr(loader, "soft_targets") else None
 
 
 def _scheduled_lr(optimizer):
@@ -59,10 +84,11 @@ def micro_batch_ctx(model, first, last):
 
 
 def _groups(loader, k):
-    """The loader's batches in groups of ``k`` (the last group may be shorter)."""
+    """The loader's batches in groups of ``k`` (the last group may be shorter), each as
+    (data, target, mix) with ``mix`` = the batch's mixup partner labels and lam, or None."""
     group = []
-    for item in loader:
-        group.append(item)
+    for data, target in loader:
+        group.append((data, target, batch_mix(loader)))
         if len(group) == k:
             yield group
             group = []
@@ -103,9 +129,10 @@ class _Iterations:
         self.start = time.perf_counter_ns()
         self.lr = _scheduled_lr(self.optimizer)
 
-    def end(self, it, m, mean_loss):
+    def end(self, it, m, mean_loss, lam=None):
         """``mean_loss()``: the value of the loss line, asked for when one is due; returns
-        whether it was (the caller then starts its running mean anew)."""
+        whether it was (the caller then starts its running mean anew). ``lam``: with mixup the
+        mixing weights of the iteration's micro-batches (a list with accumulation)."""
         due = it % 20 == 19
         if due:
             self.log(f'[{self.epoch + 1}, {it + 1:5d}] loss: {mean_loss():.3f}')
@@ -120,7 +147,8 @@ class _Iterations:
         if self.metrics is not None:
             self.metrics.log(event="iter", epoch=self.epoch, batch=it, ns=dt,
                              **({"accum": m} if self.accum else {}), **self.lr,
-                             **_guard_stats(self.optimizer))
+                             **_guard_stats(self.optimizer),
+                             **({"lam": lam if self.accum else lam[0]} if lam else {}))
         if self.watchdog is not None:
             self.watchdog.beat()
         return due
@@ -144,7 +172,7 @@ def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", 
         book.begin(it)
         m = len(group)
         losses = []
-        for j, (data, target) in enumerate(group):
+        for j, (data, target, mix) in enumerate(group):
             with trace_range("data"):
                 data, target = data.to(device), target.to(device)
             if j == 0:
@@ -152,7 +180,7 @@ def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", 
             with micro_batch_ctx(model, j == 0, j == m - 1):
                 with trace_range("forward"):
                     output = model(data)
-                    loss = criterion(output, target)
+                    loss = criterion(output, target, mix) if mix else criterion(output, target)
                 with trace_range("backward"):
                     (loss if fused or m == 1 else loss / m).backward()
             losses.append(loss.detach())
@@ -163,7 +191,8 @@ def train_model(model, train_loader, optimizer, criterion, epoch, device="cpu", 
             optimizer.step()
 
         running_loss += sum(v.item() for v in losses) / m
-        if book.end(it, m, lambda: running_loss / 20):
+        lam = [float(mix[1]) for _, _, mix in group if mix] if metrics is not None else None
+        if book.end(it, m, lambda: running_loss / 20, lam):
             running_loss = 0.0
     return book.stats
 
@@ -202,11 +231,12 @@ def train_model_graph(step, train_loader, epoch, log=print, metrics=None, watchd
             m = K
         else:
             m = len(sizes)
-            step.tail_step([train_loader.batch((replays * K + j) * B, n)
-                            for j, n in enumerate(sizes)])
+            step.tail_step([(*train_loader.batch((replays * K + j) * B, n),
+                             batch_mix(train_loader)) for j, n in enumerate(sizes)])
         micro += m
         torch.cuda.synchronize()
-        if book.end(it, m, lambda: step.pop_loss() / micro):
+        lam = step.lams() if metrics is not None and hasattr(step, "lams") else None
+        if book.end(it, m, lambda: step.pop_loss() / micro, lam):
             micro = 0
     if hasattr(step, "check_error"):
         step.check_error()
@@ -243,6 +273,8 @@ def test_model(model, test_loader, criterion, device="cpu", log=print, watchdog=
     inner = getattr(model, "module", model)
     fused = (torch.device(device).type == "cuda" and hasattr(inner, "forward_metrics")
              and type(criterion) is CrossEntropyLoss)
+    if type(criterion) is CrossEntropyLoss:
+        criterion = CrossEntropyLoss()  # evaluation is the plain loss: no smoothing, no mixup
     if fused:  # loss + argmax hits accumulated on the device by the classifier kernel
         loss_acc = torch.zeros((), dtype=torch.float32, device=device)
         hits = torch.zeros((), dtype=torch.int32, device=device)

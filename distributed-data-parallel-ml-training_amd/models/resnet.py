@@ -177,7 +177,7 @@ class ResNet(nn.Module):
             return self.conv1.weight
         return list(self.blocks())[i - 1].conv1.weight
 
-    def forward_loss_split(self, x, labels, split, acc=None, transient=False):
+    def forward_loss_split(self, x, labels, split, acc=None, transient=False, soft=None):
         """Mean CE loss of the fused GPU forward, cut before stage(s) ``split`` (int or
         ascending list in 1..n_stages-1): returns (loss, cuts), cuts[k] = (h_k, leaf_k) as in
         models/vgg.py ``forward_loss_split``. A cut block input that feeds both residual
@@ -201,7 +201,7 @@ class ResNet(nn.Module):
                 cuts.append((h, leaf))
                 h = leaf
             h = self._stem_forward(h, stem) if st == 0 else blocks[st - 1].forward_fused(h)
-        loss = cross_entropy(linear_gemm(global_avg_pool(h), fc), labels)
+        loss = cross_entropy(linear_gemm(global_avg_pool(h), fc), labels, soft)
         if acc is not None:
             acc.add_(loss.detach())
         return loss, cuts

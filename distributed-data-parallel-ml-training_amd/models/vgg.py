@@ -117,14 +117,14 @@ class _VGG(nn.Module):
                                self.fc1.weight.shape[0], 0, 0, ptr(loss_acc), ptr(correct_acc),
                                stream_handle())
 
-    def forward_loss_split(self, x, labels, split, acc=None, transient=False):
+    def forward_loss_split(self, x, labels, split, acc=None, transient=False, soft=None):
         """``forward_loss`` cut after fused stage(s) ``split`` (GPU; an int or ascending list of
         stage indices): returns (loss, cuts) with cuts[k] = (h_k, leaf_k), h_k the output of the
         stages before split[k] and ``leaf_k = h_k.detach().requires_grad_()`` the input of the
         stages from split[k] on. ``loss.backward()`` produces the gradients of the stages from
         split[-1] (+ fc1) and ``h_k.backward(leaf_k.grad)`` for k = len-1 .. 0 those of each
         earlier segment — backward segments the DDP engine can put collectives between
-        (engine/step.py SegmentedDDPStep)."""
+        (engine/step.py SegmentedDDPStep). ``soft``: as in ``forward_loss``."""
         from ..ops.layers import conv_bn_act, to_nhwc_input, linear_cross_entropy
         from ..ops.common import step_scratch
         plan = self.fused_plan()
@@ -143,7 +143,7 @@ class _VGG(nn.Module):
                 h = leaf
             prev = sp
         loss = linear_cross_entropy(h.view(h.shape[0], -1), self.fc1, labels, acc, transient,
-                                    bn_prev=plan[-1])
+                                    bn_prev=plan[-1], soft=soft)
         return loss, cuts
 
     def n_stages(self):
@@ -154,14 +154,18 @@ class _VGG(nn.Module):
         """Parameter that starts fused stage ``i`` in ``parameters()`` order (its conv weight)."""
         return self.fused_plan()[i].conv.weight
 
-    def forward_loss(self, x, labels, acc=None, transient=False):
+    def forward_loss(self, x, labels, acc=None, transient=False, soft=None):
         """``CrossEntropyLoss()(self(x), labels)`` with the classifier and the loss fused into one
         kernel on the GPU (engine/step.py uses it for the captured training step). ``acc`` (fp32
         scalar) additionally accumulates the loss across calls. The returned loss tensor is only
         valid until the next forward when ``transient`` (it then lives in the per-forward
-        scratch and costs no fill launch)."""
+        scratch and costs no fill launch). ``soft``: a SoftTarget (ops/common.py: label
+        smoothing / mixup) in place of the one-hot target, in the same kernel."""
         if not x.is_cuda:
-            loss = nn.functional.cross_entropy(self.forward(x), labels)
+            if soft is not None:
+                loss = soft.torch_loss(self.forward(x), labels)
+            else:
+                loss = nn.functional.cross_entropy(self.forward(x), labels)
             if acc is not None:
                 acc.add_(loss.detach())
             return loss
@@ -172,7 +176,7 @@ class _VGG(nn.Module):
             h = self._features_fused(x)
         finally:
             last.defer_to_head = False
-        return linear_cross_entropy(h, self.fc1, labels, acc, transient, bn_prev=last)
+        return linear_cross_entropy(h, self.fc1, labels, acc, transient, bn_prev=last, soft=soft)
 
 
 def VGG11():

@@ -1,4 +1,5 @@
 """Shared helpers for the op wrappers: native handle, raw pointers, streams, grad-ready hooks."""
+import collections
 import os
 
 import torch
@@ -71,6 +72,40 @@ def ptr(t):
     if t is None:
         return 0
     return t.data_ptr()
+
+
+class SoftTarget(collections.namedtuple("SoftTarget", "smoothing labels_b lam",
+                                        defaults=(0.0, None, None))):
+    """Soft target of the loss (label smoothing E and mixup; csrc/kernels/api.h SoftTarget):
+    t_j = (1 - E) * (lam * [j == ya] + (1 - lam) * [j == yb]) + E / J, with ya the labels the
+    loss is called with, ``labels_b`` the mixup partners' (int64 [B]; None: yb = ya) and ``lam``
+    the batch's mixing weight (one fp32 value in a tensor, read by the kernel at run time so
+    that a captured step follows the table; None: 1)."""
+    __slots__ = ()
+
+    def native(self):
+        """The ``soft=`` argument of the native loss entry points."""
+        if self.labels_b is not None:
+            check(self.labels_b, torch.int64, name="mixup partner labels")
+        if self.lam is not None:
+            check(self.lam, torch.float32, name="mixup lam")
+        return (float(self.smoothing), ptr(self.labels_b), ptr(self.lam))
+
+    @property
+    def plain(self):
+        return not self.smoothing and self.labels_b is None
+
+    def torch_loss(self, logits, labels):
+        """The same loss through ATen (the CPU path and the oracle of the kernels):
+        lam * CE(ya) + (1 - lam) * CE(yb), each ``cross_entropy(label_smoothing=E)``."""
+        ce = torch.nn.functional.cross_entropy
+        e = float(self.smoothing)
+        la = ce(logits, labels, label_smoothing=e)
+        if self.labels_b is None:
+            return la
+        lam = 1.0 if self.lam is None else self.lam.to(logits.device).reshape(())
+        return lam * la + (1.0 - lam) * ce(logits, self.labels_b.to(logits.device),
+                                           label_smoothing=e)
 
 
 def stream_handle(stream=None):

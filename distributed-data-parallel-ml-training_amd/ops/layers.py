@@ -766,8 +766,10 @@ class _LinearCEFn(torch.autograd.Function):
     same kernel."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, labels, acc, transient, bn_prev=None):
+    def forward(ctx, x, weight, bias, labels, acc, transient, bn_prev=None, soft=None):
         B, F = x.shape
+        # soft targets (ops/common.py SoftTarget): the SOFT instantiation of the same kernel
+        soft = {"soft": soft.native()} if soft is not None and not soft.plain else {}
         # the Conv->BN->ReLU->pool block whose output x is: its BN backward may be fused into
         # the head's backward (conv_igemm.hip linear_head_bwd_kernel)
         ctx.bn_prev = bn_prev
@@ -787,10 +789,11 @@ class _LinearCEFn(torch.autograd.Function):
                                            ptr(bn.bias), bn_prev.eps, int(bn_prev.relu),
                                            ptr(bn_prev.coef), ptr(x), ptr(weight), ptr(bias),
                                            ptr(labels), B, F, J, ptr(dl), ptr(loss),
-                                           stream_handle(), loss_acc=ptr(acc))
+                                           stream_handle(), loss_acc=ptr(acc), **soft)
         else:
             native().linear_ce_fwd(ptr(x), ptr(weight), ptr(bias), ptr(labels), B, F, J, 0,
-                                   ptr(dl), ptr(loss), 0, stream_handle(), loss_acc=ptr(acc))
+                                   ptr(dl), ptr(loss), 0, stream_handle(), loss_acc=ptr(acc),
+                                   **soft)
         ctx.save_for_backward(x, weight, bias, dl)
         return loss
 
@@ -817,21 +820,22 @@ class _LinearCEFn(torch.autograd.Function):
             if done:  # dx never materialised: the block's backward takes dz_prev
                 prev.dz_fused = (dz_prev, pz)
                 grad_ready([weight, bias])
-                return torch.empty_like(x), None, None, None, None, None, None
+                return torch.empty_like(x), None, None, None, None, None, None, None
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         native().linear_bwd(ptr(dl), ptr(x), ptr(weight), B, F, J, ptr(g), ptr(dx), ptr(gw),
                             ptr(gb), stream_handle())
         grad_ready([weight, bias])
-        return dx, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None
 
 
-def linear_cross_entropy(x, linear, labels, acc=None, transient=False, bn_prev=None):
+def linear_cross_entropy(x, linear, labels, acc=None, transient=False, bn_prev=None, soft=None):
     """mean CE(linear(x), labels) in one kernel (J <= 16); see _LinearCEFn. ``transient=True``
     returns the loss in the per-forward scratch (saves a fill launch; valid until the next
-    model forward on this device — the captured training step uses it)."""
+    model forward on this device — the captured training step uses it). ``soft``: a SoftTarget
+    (label smoothing / mixup) in place of the one-hot target."""
     if linear.weight.shape[0] > 16:
         raise ValueError("linear_cross_entropy supports at most 16 outputs")
-    return _LinearCEFn.apply(x, linear.weight, linear.bias, labels, acc, transient, bn_prev)
+    return _LinearCEFn.apply(x, linear.weight, linear.bias, labels, acc, transient, bn_prev, soft)
 
 
 def linear_small(x, linear):
@@ -842,8 +846,9 @@ def linear_small(x, linear):
 
 class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, soft=None):
         B, J = logits.shape
+        soft = {"soft": soft.native()} if soft is not None and not soft.plain else {}
         logits = logits.contiguous()
         if logits.dtype not in (F32, BF16):
             raise ValueError("logits must be fp32 or bf16")
@@ -852,19 +857,20 @@ class _CrossEntropyFn(torch.autograd.Function):
         loss = torch.zeros((), dtype=F32, device=logits.device)
         dl = torch.empty(B, J, dtype=logits.dtype, device=logits.device)  # dlogits in logits dtype
         native().softmax_ce(ptr(logits), is_bf16, ptr(labels), B, J, ptr(loss), 0, ptr(dl),
-                            is_bf16, stream_handle())
+                            is_bf16, stream_handle(), **soft)
         ctx.save_for_backward(dl)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None
+        return dl * g, None, None
 
 
-def cross_entropy(logits, labels):
-    """Mean softmax cross-entropy (reference: nn.CrossEntropyLoss(), part1/main.py:119)."""
-    return _CrossEntropyFn.apply(logits, labels)
+def cross_entropy(logits, labels, soft=None):
+    """Mean softmax cross-entropy (reference: nn.CrossEntropyLoss(), part1/main.py:119);
+    ``soft``: a SoftTarget (label smoothing / mixup) in place of the one-hot target."""
+    return _CrossEntropyFn.apply(logits, labels, soft)
 
 
 def to_nhwc_input(x, cpad=8):

@@ -88,7 +88,30 @@ def build_parser(description=None, distributed=True):
                    help='gradient accumulation: one optimizer step consumes this many consecutive '
                         'batches of --global-batch samples (effective batch = global batch x K; one '
                         'gradient sync and one update per K backward passes; works inside --graph)')
+    g.add_argument('--label-smoothing', type=_label_smoothing, default=0.0,
+                   help='training loss against (1 - E) * target + E / classes, 0 <= E < 1 '
+                        '(torch label_smoothing; inside the fused loss kernels, works inside '
+                        '--graph; evaluation stays the plain loss); default 0')
+    g.add_argument('--mixup-alpha', type=_mixup_alpha, default=0.0,
+                   help='mixup: every training batch is blended with itself reversed by lam ~ '
+                        'Beta(A, A), one draw per batch from a per-epoch table, inside the batch '
+                        'kernel, and the loss is lam * CE(y) + (1 - lam) * CE(y reversed) (works '
+                        'inside --graph); default 0 = off')
     return p
+
+
+def _label_smoothing(v):
+    e = float(v)
+    if not 0.0 <= e < 1.0:
+        raise argparse.ArgumentTypeError("--label-smoothing must be in [0, 1)")
+    return e
+
+
+def _mixup_alpha(v):
+    a = float(v)
+    if not (a >= 0.0 and a != float("inf")):
+        raise argparse.ArgumentTypeError("--mixup-alpha must be a finite number >= 0")
+    return a
 
 
 def _accum_steps(v):
