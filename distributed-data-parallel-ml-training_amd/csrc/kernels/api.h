@@ -277,6 +277,16 @@ struct ClipArgs {
   float* stats;          // 4 words {norm, coefficient, skipped steps (u32), -}, stored by block 0
 };
 
+// Weight EMA (optim/sgd.py set_ema): ``ema`` non-null selects the EMA instantiations. The arena
+// has the masters' element index; every element whose master the launch updates takes
+//     e = fma(one_minus_decay, p_new - e, e)        (p_new == e leaves e as it is, to the bit)
+// in the same pass, from the new p in registers. A launch that updates nothing (the ``skip``
+// word, a step the guard skipped) and item kinds 4 and 5 leave it alone.
+struct EmaArgs {
+  float* ema;
+  float one_minus_decay;  // float32(1 - decay), rounded once on the host
+};
+
 struct UpdateLaunch {
   const int4* items;      // work items, kinds 0-5 (optim.hip), one block each
   int n_items;
@@ -287,6 +297,7 @@ struct UpdateLaunch {
   SgdHyper h;
   LarsArgs lars;          // optional: lars.side == null
   ClipArgs clip;          // optional: clip.partial == null
+  EmaArgs ema;            // optional: ema.ema == null
 };
 
 struct AugArgs {

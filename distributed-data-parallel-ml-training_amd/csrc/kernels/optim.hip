@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 // ---------------------------------------------------------------------------------------------
 // Fused SGD + weight re-pack: ONE launch updates the whole arena and writes the bf16 MFMA
 // operand copies of every conv weight from the freshly updated values (no second pass over the
-// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD>, one block per work item (int4):
+// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD, EMA>, one block per work item (int4):
 //   {0, offset, count, -}        plain elementwise chunk;
 //   {2, rel_offset, count, desc} elementwise chunk of a conv weight stored [K][R][S][C] (the GPU
 //                                arena layout, C == Cr, or 1x1): its bf16 copy Wc has the same
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 //   {5, rel_offset, count, desc} operand re-pack only — the fp32 master was already updated by
 //                                the backward (conv_igemm.hip ConvArgs::sgd); bf16(p) into the
 //                                operand copy (as item 2).
-// Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs.
+// Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs, EmaArgs.
 constexpr int kTileElems = 9216;  // fp32 LDS tile (36 KB)
 
 __host__ __device__ __forceinline__ void tile_dims(int RS, int* TK, int* TC) {
@@ -177,14 +177,41 @@ __device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper
   }
 }
 
+// Weight EMA (api.h EmaArgs) of the elements the launch updates, in the same pass: the new p is
+// in registers, so the average costs one read and one write of its own arena and no launch.
+// The lerp form keeps e to the bit where p_new == e; two roundings, the subtraction and the fma.
+// EMA = false: an empty argument and no code (the plain instantiations compile to what they were).
+struct NoEma {};
+template <bool EMA>
+using EmaOf = std::conditional_t<EMA, EmaArgs, NoEma>;
+
+__device__ __forceinline__ float ema_lerp(float e, float np, float one_minus_decay) {
+  return __builtin_fmaf(one_minus_decay, np - e, e);
+}
+
+// One element, by its arena index.
+template <bool EMA>
+__device__ __forceinline__ void ema1(const EmaOf<EMA>& m, size_t i, float np) {
+  if constexpr (EMA) m.ema[i] = ema_lerp(m.ema[i], np, m.one_minus_decay);
+}
+
+// The EMA's element of arena index i (null without EMA: never read).
+template <bool EMA>
+__device__ __forceinline__ float* ema_at(const EmaOf<EMA>& m, size_t i) {
+  if constexpr (EMA) return m.ema + i;
+  else return nullptr;
+}
+
 // The update of four elements (16-byte aligned) on float4 registers: p and buf stored, +0 into
-// g under zero_grad; returns the new p.
-template <bool LARS>
+// g under zero_grad, the EMA of the four (``e``: ema_at of the same index); returns the new p.
+template <bool LARS, bool EMA>
 __device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, const SgdHyper& h,
-                                       float trust) {
+                                       float trust, float* e, const EmaOf<EMA>& m) {
   float4 pv = *reinterpret_cast<float4*>(p);
   const float4 gv = *reinterpret_cast<const float4*>(g);
   float4 bv = *reinterpret_cast<float4*>(buf);
+  float4 ev;  // (unused without EMA)
+  if constexpr (EMA) ev = *reinterpret_cast<const float4*>(e);
   pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
   pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
   pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
@@ -192,6 +219,13 @@ __device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, const Sgd
   *reinterpret_cast<float4*>(p) = pv;
   *reinterpret_cast<float4*>(buf) = bv;
   if (h.zero_grad) *reinterpret_cast<float4*>(g) = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (EMA) {
+    ev.x = ema_lerp(ev.x, pv.x, m.one_minus_decay);
+    ev.y = ema_lerp(ev.y, pv.y, m.one_minus_decay);
+    ev.z = ema_lerp(ev.z, pv.z, m.one_minus_decay);
+    ev.w = ema_lerp(ev.w, pv.w, m.one_minus_decay);
+    *reinterpret_cast<float4*>(e) = ev;
+  }
   return pv;
 }
 
@@ -418,12 +452,13 @@ __device__ __forceinline__ void guard_clear(const int4& it, const ConvDesc* __re
   for (int i = threadIdx.x; i < it.z; i += 256) gp[i] = 0.f;
 }
 
-template <bool LARS, bool GUARD>
+template <bool LARS, bool GUARD, bool EMA>
 __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
                                               const ConvDesc* __restrict__ descs,
                                               float* __restrict__ p, float* __restrict__ g,
                                               float* __restrict__ buf, const SgdHyper& h,
-                                              float* tile, float trust, const GuardState& gd) {
+                                              float* tile, float trust, const GuardState& gd,
+                                              const EmaOf<EMA>& m) {
   const int4 it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
@@ -448,13 +483,16 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t off = elem_offset(it, descs);
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
         if (i + 4 <= cnt && ((off + i) & 3) == 0) {
-          sgd4<LARS>(p + off + i, g + off + i, buf + off + i, h, trust);
+          sgd4<LARS, EMA>(p + off + i, g + off + i, buf + off + i, h, trust,
+                          ema_at<EMA>(m, off + i), m);
         } else {
           for (int e = i; e < min(cnt, i + 4); ++e) {
             float b = buf[off + e];
-            p[off + e] = sgd1<LARS>(p[off + e], g[off + e], b, h, trust);
+            const float np = sgd1<LARS>(p[off + e], g[off + e], b, h, trust);
+            p[off + e] = np;
             buf[off + e] = b;
             if (h.zero_grad) g[off + e] = 0.f;
+            ema1<EMA>(m, off + e, np);
           }
         }
       }
@@ -464,7 +502,8 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t off = elem_offset(it, descs);
       float* slot = it.w >= 0 && h.slot ? h.slot + it.w : nullptr;
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
-        const float4 pv = sgd4<LARS>(p + off + i, g + off + i, buf + off + i, h, trust);
+        const float4 pv = sgd4<LARS, EMA>(p + off + i, g + off + i, buf + off + i, h, trust,
+                                          ema_at<EMA>(m, off + i), m);
         if (h.shadow) *reinterpret_cast<uint2*>(h.shadow + off + i) = bf16x4(pv);
         if (slot) *reinterpret_cast<float4*>(slot + i) = pv;
       }
@@ -480,7 +519,8 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t base = elem_offset(it, descs);
       unsigned short* wc = descs[it.w].wc + (unsigned)it.y;
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
-        const float4 pv = sgd4<LARS>(p + base + i, g + base + i, buf + base + i, h, trust);
+        const float4 pv = sgd4<LARS, EMA>(p + base + i, g + base + i, buf + base + i, h, trust,
+                                          ema_at<EMA>(m, base + i), m);
         *reinterpret_cast<uint2*>(wc + i) = bf16x4(pv);
       }
       break;
@@ -502,6 +542,7 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
         p[gi] = np;
         buf[gi] = b;
         if (h.zero_grad) g[gi] = 0.f;
+        ema1<EMA>(m, gi, np);  // (the arena index, as p: the EMA has the masters' layout)
         tile[li] = np;
       });
       __syncthreads();
@@ -528,24 +569,30 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
 }
 
 // The kernel's arguments behind the tables and arenas (their __restrict__ keeps the table reads
-// scalar): SgdHyper, then LarsArgs and ClipArgs only in the instantiations that read them (an
-// empty base takes no kernarg bytes; an empty struct argument would).
+// scalar): SgdHyper, then LarsArgs, ClipArgs and EmaArgs only in the instantiations that read
+// them (an empty base takes no kernarg bytes; an empty struct argument would).
 struct NoLars {};
 struct NoClip {};
-template <bool LARS, bool GUARD>
+template <bool LARS, bool GUARD, bool EMA>
 struct UpdateArgs : SgdHyper, std::conditional_t<LARS, LarsArgs, NoLars>,
-                    std::conditional_t<GUARD, ClipArgs, NoClip> {};
-static_assert(sizeof(UpdateArgs<false, false>) == 96 && sizeof(UpdateArgs<false, true>) == 128 &&
-              sizeof(UpdateArgs<true, false>) == 136 && sizeof(UpdateArgs<true, true>) == 168,
-              "kernarg bytes of the four instantiations");
+                    std::conditional_t<GUARD, ClipArgs, NoClip>, EmaOf<EMA> {};
+static_assert(sizeof(UpdateArgs<false, false, false>) == 96 &&
+              sizeof(UpdateArgs<false, true, false>) == 128 &&
+              sizeof(UpdateArgs<true, false, false>) == 136 &&
+              sizeof(UpdateArgs<true, true, false>) == 168 &&
+              sizeof(UpdateArgs<false, false, true>) == 112 &&
+              sizeof(UpdateArgs<false, true, true>) == 144 &&
+              sizeof(UpdateArgs<true, false, true>) == 152 &&
+              sizeof(UpdateArgs<true, true, true>) == 184,
+              "kernarg bytes of the eight instantiations");
 
-template <bool LARS, bool GUARD>
+template <bool LARS, bool GUARD, bool EMA>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
                                                        const ConvDesc* __restrict__ descs,
                                                        float* __restrict__ p,
                                                        float* __restrict__ g,
                                                        float* __restrict__ buf,
-                                                       UpdateArgs<LARS, GUARD> a) {
+                                                       UpdateArgs<LARS, GUARD, EMA> a) {
   __shared__ float tile[kTileElems];
   SgdHyper h = a;
   h.lr = sched_lr_block(h.sched, h.lr);
@@ -556,7 +603,7 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
   // (a skipped step leaves the stored ratios as they are)
   if constexpr (LARS) trust = GUARD && gd.skipped ? 1.f : lars_trust_block<GUARD>(a, h.wd, gd.c);
   if constexpr (GUARD) h.grad_scale *= gd.c;
-  sgd_pack_body<LARS, GUARD>(items, descs, p, g, buf, h, tile, trust, gd);
+  sgd_pack_body<LARS, GUARD, EMA>(items, descs, p, g, buf, h, tile, trust, gd, a);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
@@ -610,14 +657,15 @@ __global__ void counter_add_kernel(int* c, int delta, LrSched* sched, int sched_
   __hip_atomic_store(&sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool LARS, bool GUARD>
+template <bool LARS, bool GUARD, bool EMA>
 static int launch_update(const UpdateLaunch& u, hipStream_t st) {
-  UpdateArgs<LARS, GUARD> a{};
+  UpdateArgs<LARS, GUARD, EMA> a{};
   static_cast<SgdHyper&>(a) = u.h;
   a.sched_advance = a.sched && a.sched_advance ? 1 : 0;
   if constexpr (LARS) static_cast<LarsArgs&>(a) = u.lars;
   if constexpr (GUARD) static_cast<ClipArgs&>(a) = u.clip;
-  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD>), dim3(u.n_items), dim3(256), 0, st, u.items,
+  if constexpr (EMA) static_cast<EmaArgs&>(a) = u.ema;
+  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA>), dim3(u.n_items), dim3(256), 0, st, u.items,
                      u.descs, u.p, u.g, u.buf, a);
   return (int)hipGetLastError();
 }
@@ -670,8 +718,11 @@ extern "C" int ddp_sgd_pack(const UpdateLaunch* u, hipStream_t st) {
   const bool lars = u->lars.side, guard = u->clip.partial;
   if (guard && (!u->clip.stats || u->clip.n_chunks < 0)) return -1;
   if (lars && (!u->lars.tensors || !u->lars.partial || !u->lars.trust)) return -1;
-  return (lars ? (guard ? launch_update<true, true> : launch_update<true, false>)
-               : (guard ? launch_update<false, true> : launch_update<false, false>))(*u, st);
+  if (u->ema.ema)
+    return (lars ? (guard ? launch_update<true, true, true> : launch_update<true, false, true>)
+                 : (guard ? launch_update<false, true, true> : launch_update<false, false, true>))(*u, st);
+  return (lars ? (guard ? launch_update<true, true, false> : launch_update<true, false, false>)
+               : (guard ? launch_update<false, true, false> : launch_update<false, false, false>))(*u, st);
 }
 
 extern "C" int ddp_grad_sumsq(const void* items, int n_items, const float* g, float grad_scale,

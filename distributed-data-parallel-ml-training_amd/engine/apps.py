@@ -66,8 +66,15 @@ def main(part, argv=None):
     optimizer = optimizer_from_args(args, model.parameters(), lr)  # --optimizer sgd | lars
     if schedule is not None:
         optimizer.set_schedule(schedule)
+    # --ema-decay (opt-in): the average starts as a copy of the weights, so it is switched on
+    # once they are final: after the DDP wrapper's rank-0 broadcast and after --resume (which
+    # restores the checkpoint's average, or seeds it from the loaded weights)
+    ema_decay = args.ema_decay or None
     if args.resume:
-        load_checkpoint(args.resume, model, optimizer)
+        load_checkpoint(args.resume, model, optimizer, ema_decay=ema_decay)
+    elif ema_decay:
+        optimizer.set_ema(ema_decay)
+    ema_on = optimizer.ema_decay is not None  # (a resumed optimizer may carry its own)
     sync = None
     if strategy in STRATEGIES:
         sync = functools.partial(_sync, STRATEGIES[strategy], comm)
@@ -88,7 +95,8 @@ def main(part, argv=None):
         # it back after the capture, so the epoch starts exactly where the eager loop would
         from .step import TrainStep, SegmentedDDPStep, default_cuts
         arena = model.arena if hasattr(model, "arena") else optimizer.arena
-        snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), optimizer.lr_step)
+        snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), optimizer.lr_step,
+                optimizer.ema.clone() if ema_on else None)
         split = [int(v) for v in os.environ.get("DDP_AMD_SEGMENTED",
                                                 default_cuts(args.model, batch_size)).split(",")
                  if int(v) > 0]
@@ -111,6 +119,8 @@ def main(part, argv=None):
         arena.data.copy_(snap[0])
         optimizer.momentum_buffer.copy_(snap[1])
         optimizer.set_lr_step(snap[2])  # the warm-up / validation steps used no schedule entry
+        if ema_on:
+            optimizer.ema.copy_(snap[3])  # ... and averaged nothing
         optimizer.repack()
         train_loader.cursor.zero_()
         del snap
@@ -129,6 +139,12 @@ def main(part, argv=None):
                         accum_steps=args.accum_steps)
         if not args.no_test:
             test_model(model, test_loader, criterion, device, watchdog=watchdog)
+            if ema_on:
+                # a second pass on the averaged weights (BatchNorm buffers are not averaged:
+                # the model's current ones); the swap back restores every weight bit for bit
+                with optimizer.ema_weights():
+                    test_model(model, test_loader, criterion, device, watchdog=watchdog,
+                               tag=" (EMA)")
 
     if args.save and rank == 0:
         save_checkpoint(args.save, model, optimizer)

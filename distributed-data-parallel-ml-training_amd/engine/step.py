@@ -94,9 +94,11 @@ class TrainStep:
         # finish that completes its gradient; the step's SGD launch covers only the rest
         # (optim/sgd.py register_in_backward). DDP_AMD_SGD_IN_BWD=0 keeps the separate pass.
         # LARS needs the norm of the whole gradient before any element moves: never in the backward.
+        # The weight EMA is advanced by the step's update launch: every update runs there.
         self.opt_in_bwd = (self.fold_opt and sync is None and sgd_in_backward_ok(model)
                            and hasattr(optimizer, "register_in_backward")
                            and not getattr(optimizer, "needs_whole_tensors", False)
+                           and not getattr(optimizer, "updates_in_launch_only", False)
                            and self.accum_steps == 1)
         if self.accum_steps > 1 and not self.fold_opt:
             raise ValueError("accum_steps > 1 needs the fused optimizer and the device loader "
@@ -337,6 +339,10 @@ class SegmentedDDPStep(TrainStep):
     advance, the D signal and the schedule staging. The price: the update is no longer hidden
     under the backward. The sharded plans refuse such an optimizer.
 
+    With the optimizer's weight EMA (optim/sgd.py ``set_ema``) each bucket's update launch
+    advances the average of its own parameters, and the guard's whole-arena launch that of all;
+    the sharded plans refuse such an optimizer too.
+
     The DDP wrapper's own reducer is bypassed (``no_sync``). World size 1 has no collective
     unless ``emulate`` > 0 (bucket-sized stand-in passes) or ``emulate_gbps`` > 0 (a 32-CU
     stand-in lasting bytes / emulate_gbps that then multiplies the bucket by ``emulate_scale``:
@@ -433,6 +439,12 @@ class SegmentedDDPStep(TrainStep):
                                 if getattr(optimizer, "guarded", False) else "")
                              + ": the sharded updates (zero=True, \"s16\" buckets) split them "
                              "across ranks; use update=\"allreduce\"")
+        if getattr(optimizer, "updates_in_launch_only", False) and (zero or "s16" in update):
+            # the weight EMA is taken in the replicated update launches: each bucket's launch
+            # carries it for its own items, the guard's whole-arena launch for all of them
+            raise ValueError(f"{type(optimizer).__name__} with a weight EMA: the sharded updates "
+                             "(zero=True, \"s16\" buckets) do not advance it; use "
+                             "update=\"allreduce\"")
         self.zero = None
         self.shard16 = None
         if zero:
@@ -727,6 +739,7 @@ def profile_stage_times(ddp, optimizer, criterion, loader, n_stages, reps=4):
     parallel/cut_plan.plan_cuts."""
     arena = ddp.arena
     snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), loader.cursor.clone())
+    ema = optimizer.ema.clone() if getattr(optimizer, "ema_decay", None) is not None else None
     lr_step = getattr(optimizer, "lr_step", 0)  # the profiled steps must not use the schedule up
     # module buffers too (ResNet's BatchNorm running statistics): the profiling batches must
     # not leave extra updates behind
@@ -751,6 +764,8 @@ def profile_stage_times(ddp, optimizer, criterion, loader, n_stages, reps=4):
         arena.data.copy_(snap[0])
         optimizer.momentum_buffer.copy_(snap[1])
         loader.cursor.copy_(snap[2])
+        if ema is not None:
+            optimizer.ema.copy_(ema)
         if hasattr(optimizer, "set_lr_step"):
             optimizer.set_lr_step(lr_step)
         for b, v in zip(bufs, bsnap):

@@ -72,6 +72,12 @@ def _guard_stats(optimizer):
             "skipped": int(optimizer.skipped_steps())}
 
 
+def _ema_field(optimizer):
+    """Extra metrics field of one iteration with the optimizer's weight EMA on (set_ema)."""
+    d = getattr(optimizer, "ema_decay", None)
+    return {} if d is None else {"ema_decay": d}
+
+
 def micro_batch_ctx(model, first, last):
     """DDP wrapper state of one micro-batch of an accumulated step: no gradient collective
     before the last one (``no_sync``), the buffer broadcast only before the first one."""
@@ -147,7 +153,7 @@ class _Iterations:
         if self.metrics is not None:
             self.metrics.log(event="iter", epoch=self.epoch, batch=it, ns=dt,
                              **({"accum": m} if self.accum else {}), **self.lr,
-                             **_guard_stats(self.optimizer),
+                             **_guard_stats(self.optimizer), **_ema_field(self.optimizer),
                              **({"lam": lam if self.accum else lam[0]} if lam else {}))
         if self.watchdog is not None:
             self.watchdog.beat()
@@ -265,7 +271,9 @@ def graph_epoch_plan(n_samples, batch_size, max_batches=None):
     return nfull, tail
 
 
-def test_model(model, test_loader, criterion, device="cpu", log=print, watchdog=None):
+def test_model(model, test_loader, criterion, device="cpu", log=print, watchdog=None, tag=""):
+    """``tag``: appended to ``Test set`` in the result line (`` (EMA)``: the pass on the
+    averaged weights, engine/apps.py); empty: the reference's line."""
     model.eval()
     test_loss = 0
     correct = 0
@@ -295,7 +303,7 @@ def test_model(model, test_loader, criterion, device="cpu", log=print, watchdog=
         test_loss, correct = float(loss_acc), int(hits)
     n = len(test_loader.dataset)
     test_loss = float(test_loss) / max(nb, 1)
-    log('Test set: Average loss: {:.4f}, Accuracy: {}/{} ({:.0f}%)\n'.format(
-        test_loss, correct, n, 100. * correct / n))
+    log('Test set{}: Average loss: {:.4f}, Accuracy: {}/{} ({:.0f}%)\n'.format(
+        tag, test_loss, correct, n, 100. * correct / n))
     model.train()
     return test_loss, correct

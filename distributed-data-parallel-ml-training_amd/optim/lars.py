@@ -33,6 +33,9 @@ With the gradient guard of FusedSGD (``max_grad_norm``, ``skip_nonfinite``; opti
 first. The ratio takes c * gn as the gradient norm (sum (g gs c)^2 = c^2 sum (g gs)^2: no
 second pass over the gradient) and the update runs with gs * c. Launch order: sum of squares,
 LARS norms, the clipped LARS update.
+
+With the weight EMA of FusedSGD (``set_ema``): the same launch advances the average from the
+new master; nothing else changes (LARS already keeps every update in the step's launch).
 """
 import torch
 
@@ -182,6 +185,7 @@ class LARS(FusedSGD):
                 self._cpu_lr()
             else:
                 self._cpu_step(params, c)
+                self._cpu_ema(params)
             if lr_advance:
                 self.count_step()
             if zero_grad:

@@ -37,9 +37,26 @@ global norm would need one more collective); ``update="allreduce"`` is the plan 
 CPU the norm is taken in fp64 and rounded once to fp32 (the oracle of the kernels), the
 gradients are multiplied by gs * c in place and torch.optim.SGD does the rest (the unguarded
 CPU path is torch.optim.SGD as is and, as before, does not apply ``grad_scale``).
+
+Weight EMA (``set_ema(decay)``; opt-in): an exponential moving average of the masters in an
+fp32 arena of its own with the masters' element index, advanced once per optimizer step,
+
+    e = fma(1 - decay, p_new - e, e)      (fp32; 1 - decay rounded once on the host from fp64)
+
+the lerp form, which leaves e as it is, to the bit, where p_new == e. The masters change inside
+a replayed graph, so on the GPU the average is taken in the update launch itself (api.h EmaArgs,
+the EMA instantiations of ``sgd_pack_kernel``): the new p is in registers, the cost is one read
+and one write of the EMA arena and no dispatch. A step that updates nothing (the ``skip`` word,
+a step the guard skipped) leaves it alone. Every update has to run in that launch then
+(``updates_in_launch_only``): no SGD in the backward — its WGRAD finishes would need a fourth
+pointer in every conv kernel's arguments — and no sharded update. ``swap_ema`` exchanges
+masters and average in place (addresses stay: captured graphs stay valid) for evaluation and
+checkpoints. On the CPU the same formula runs after each step that was not skipped.
 """
+import contextlib
 import itertools
 
+import numpy as np
 import torch
 
 from .arena import arena_for
@@ -49,6 +66,38 @@ _GUARD_SHARDED = ("gradient clipping / non-finite step skipping needs the norm o
                   "gradient: after a reduce-scatter a rank holds only a shard of it, and a global "
                   "norm would need one more collective; use the replicated update, "
                   "update=\"allreduce\"")
+_EMA_LAUNCH_ONLY = ("the weight EMA is advanced by the step's own update launch, from the new "
+                    "master in its registers: ")
+_EMA_SHARDED = (_EMA_LAUNCH_ONLY + "the sharded updates (ZeRO-1, the bf16-gather update) and "
+                "element-range updates do not carry it; use the replicated update, "
+                "update=\"allreduce\"")
+
+
+def one_minus_decay(decay):
+    """float32(1 - decay): the subtraction in fp64, rounded once (the kernel's argument)."""
+    return float(np.float32(1.0 - float(decay)))
+
+
+def fma32(a, b, c):
+    """fp32 fma(a, b, c) of fp32 tensors (``a`` may be a Python float holding an fp32 value),
+    correctly rounded: the product is exact in fp64, the fp64 sum is rounded to odd (its TwoSum
+    error says whether it was inexact), and a round-to-odd value with 29 spare bits rounds to
+    fp32 as the exact sum would."""
+    a64 = a.double() if torch.is_tensor(a) else float(a)
+    prod, c64 = b.double() * a64, c.double()
+    s = c64 + prod
+    bb = s - c64
+    err = (c64 - (s - bb)) + (prod - bb)
+    even = (s.view(torch.int64) & 1) == 0
+    inf = torch.full_like(s, float("inf"))
+    odd = torch.nextafter(s, torch.where(err > 0, inf, -inf))
+    return torch.where((err != 0) & even, odd, s).float()
+
+
+def ema_lerp(e, p, omd):
+    """The EMA's step on fp32 tensors, as the update kernel takes it: fma(omd, p - e, e) with
+    ``omd`` = ``one_minus_decay(decay)``; two roundings, the subtraction and the fma."""
+    return fma32(omd, p - e, e)
 
 
 class FusedSGD(torch.optim.SGD):
@@ -87,6 +136,8 @@ class FusedSGD(torch.optim.SGD):
         self._elem_tables = {}
         self._guard_cpu = [float("nan"), 1.0, 0]  # norm, coefficient, skipped steps
         self._set_guard(max_grad_norm, clip_eps, skip_nonfinite)
+        self._ema = None        # the EMA arena (set_ema allocates it once)
+        self._ema_decay = None  # None: off
 
     @property
     def grad_scale_factor(self):
@@ -234,6 +285,153 @@ class FusedSGD(torch.optim.SGD):
                 if p.grad is not None:
                     p.grad.mul_(f)
 
+    # ------------------------------------------------------------------------------ weight EMA
+    def _ema_layout(self):
+        """(offsets, total) of the EMA arena: the parameter arena's where there is one (GPU, or
+        the DDP wrapper's on the CPU), else the parameters back to back."""
+        if self.arena is not None:
+            return self.arena.offsets, self.arena.total
+        numels = [p.numel() for p in self.param_groups[0]["params"]]
+        off = list(itertools.accumulate(numels, initial=0))
+        return off[:-1], off[-1]
+
+    def _ema_view(self, i):
+        """Tensor i of the EMA arena in the parameter's logical shape."""
+        if self.arena is not None:
+            return self.arena.shaped(self._ema, i)
+        p = self.param_groups[0]["params"][i]
+        o = self._ema_layout()[0][i]
+        return self._ema[o:o + p.numel()].view(p.shape)
+
+    def set_ema(self, decay):
+        """Switch the weight EMA on with ``0 < decay < 1`` (``None``: off). The EMA arena is
+        allocated ONCE, so its address survives re-captures, and seeded with a copy of the
+        current masters: call it once the weights are final (after the DDP wrapper's rank-0
+        broadcast, after a checkpoint load). ``ema_decay`` lives in ``param_groups[0]`` only
+        when the EMA is on: a plain optimizer's state_dict is what it was. The decay is a
+        launch argument (capture after changing it)."""
+        g = self.param_groups[0]
+        if decay is None:
+            self._ema_decay = None
+            g.pop("ema_decay", None)
+            self.defaults.pop("ema_decay", None)
+            return
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError("ema decay must be in (0, 1)")
+        if len(self.param_groups) != 1:
+            raise ValueError("the weight EMA supports a single param group")
+        params = g["params"]
+        if self._ema is None:
+            total = self._ema_layout()[1]
+            self._ema = torch.zeros(total, dtype=torch.float32, device=params[0].device)
+        with torch.no_grad():
+            if self.arena is not None:
+                self._ema.copy_(self.arena.data)
+            else:
+                for i, p in enumerate(params):
+                    self._ema_view(i).copy_(p.detach())
+        self._ema_decay = decay
+        g["ema_decay"] = decay
+        self.defaults["ema_decay"] = decay
+
+    @property
+    def ema_decay(self):
+        """The EMA's decay, or None when it is off."""
+        return self._ema_decay
+
+    @property
+    def ema(self):
+        """The EMA arena: flat fp32, the masters' element index (None before ``set_ema``)."""
+        return self._ema
+
+    @property
+    def updates_in_launch_only(self):
+        """Every update of this optimizer has to run in the step's own update launch (the
+        weight EMA is taken there): no SGD in the backward, no sharded or element-range update."""
+        return self._ema_decay is not None
+
+    def _ema_kw(self):
+        """Extra arguments of a native update launch: none with the EMA off (the launch is then
+        exactly the plain one)."""
+        if self._ema_decay is None:
+            return {}
+        return {"ema": self._ema.data_ptr(),
+                "ema_one_minus_decay": one_minus_decay(self._ema_decay)}
+
+    @torch.no_grad()
+    def _cpu_ema(self, rng=None):
+        """CPU: advance the EMA of parameters ``rng`` (default: all) after a step that was taken."""
+        if self._ema_decay is None:
+            return
+        omd = one_minus_decay(self._ema_decay)
+        params = self.param_groups[0]["params"]
+        for i in range(*(rng if rng is not None else (0, len(params)))):
+            if params[i].grad is None:
+                continue
+            e = self._ema_view(i)
+            e.copy_(ema_lerp(e.contiguous(), params[i].detach().float().contiguous(), omd))
+
+    def _need_ema(self):
+        if self._ema_decay is None:
+            raise RuntimeError("the weight EMA is off (set_ema)")
+
+    def ema_state(self, model=None):
+        """The EMA per parameter, fp32 on the host in the parameter's logical shape: under the
+        ``model``'s state_dict keys, or under the optimizer state_dict's parameter indices."""
+        self._need_ema()
+        params = self.param_groups[0]["params"]
+        keys = self._ema_keys(model)
+        return {keys[i]: self._ema_view(i).detach().cpu().contiguous().clone()
+                for i in range(len(params))}
+
+    def _ema_keys(self, model):
+        params = self.param_groups[0]["params"]
+        if model is None:
+            return list(range(len(params)))
+        name = {id(p): k for k, p in model.named_parameters()}
+        missing = [i for i, p in enumerate(params) if id(p) not in name]
+        if missing:
+            raise KeyError(f"parameters {missing} of the optimizer are not the model's")
+        return [name[id(p)] for p in params]
+
+    @torch.no_grad()
+    def load_ema_state(self, state, model=None):
+        """Inverse of ``ema_state``: every parameter's entry is required."""
+        self._need_ema()
+        for i, k in enumerate(self._ema_keys(model)):
+            v = state[k] if k in state else state[str(k)]
+            e = self._ema_view(i)
+            e.copy_(torch.as_tensor(v).to(torch.float32).reshape(e.shape))
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the masters and the EMA in place and rebuild the bf16 operand copies from
+        the new masters. Addresses stay, so captured graphs stay valid; two swaps restore the
+        masters and every operand copy bit for bit. Plumbing outside the hot path."""
+        self._need_ema()
+        if self.arena is not None:
+            tmp = self.arena.data.clone()
+            self.arena.data.copy_(self._ema)
+            self._ema.copy_(tmp)
+            if self._fused:
+                self.repack()
+            return
+        for i, p in enumerate(self.param_groups[0]["params"]):
+            e = self._ema_view(i)
+            tmp = p.detach().clone()
+            p.copy_(e)
+            e.copy_(tmp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """The model runs on the averaged weights inside (``swap_ema`` around the block)."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
     # ------------------------------------------------------------------ learning-rate schedule
     def set_schedule(self, schedule, step=0):
         """Attach an ``LRSchedule`` (``None`` detaches): from now on step k of the run uses
@@ -346,6 +544,9 @@ class FusedSGD(torch.optim.SGD):
             raise RuntimeError("gradient clipping / non-finite step skipping cannot run in the "
                                "backward: the norm exists only once the whole gradient does "
                                "(TrainStep keeps opt_in_bwd False)")
+        if self.updates_in_launch_only:
+            raise RuntimeError(_EMA_LAUNCH_ONLY + "an update taken in the backward's WGRAD "
+                               "finishes would not advance it (TrainStep keeps opt_in_bwd False)")
         from ..ops.common import native
         a, g = self.arena, self.param_groups[0]
         nat = native()
@@ -475,6 +676,8 @@ class FusedSGD(torch.optim.SGD):
         at this step for the launches that follow); ``"stage"``: as in ``step``."""
         if self.guarded:
             raise ValueError(_GUARD_SHARDED)
+        if self.updates_in_launch_only:
+            raise ValueError(_EMA_SHARDED)
         g = self.param_groups[0]
         lr, m, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
         a = self.arena
@@ -514,7 +717,8 @@ class FusedSGD(torch.optim.SGD):
         this optimizer's hyper-parameters and ``grad_scale_factor``. Step-level options as in
         ``step``; ``descs``: the table a ``_work_table`` call just returned (default: looked
         up); ``native_kw``: further native keywords (LARS', the sharded update's ``shadow`` /
-        ``slot``). The schedule's and the guard's keywords go in only when they are on."""
+        ``slot``). The schedule's, the guard's and the EMA's keywords go in only when they are
+        on."""
         from ..ops.common import native
         g, a = self.param_groups[0], self.arena
         native().sgd_pack(items.data_ptr(), n_items,
@@ -528,7 +732,8 @@ class FusedSGD(torch.optim.SGD):
                           skip=int(skip) if skip else 0,
                           done=int(signal[0]) if signal else 0,
                           signal=int(signal[1]) if signal else 0, **native_kw,
-                          **self._sched_kw(lr_advance), **self._clip_kw(lr_advance))
+                          **self._sched_kw(lr_advance), **self._clip_kw(lr_advance),
+                          **self._ema_kw())
         self._sched_commit(lr_advance, s)
 
     def repack_params(self, i0, i1, stream=None):
@@ -584,6 +789,7 @@ class FusedSGD(torch.optim.SGD):
                     return out
                 self._cpu_scale_grads(c)
             out = super().step(closure)
+            self._cpu_ema()
             if lr_advance:
                 self.count_step()
             if zero_grad:
@@ -595,6 +801,8 @@ class FusedSGD(torch.optim.SGD):
         if fused_taken:
             if self.guarded:
                 raise RuntimeError("gradient guard: no update is taken in the backward")
+            if self.updates_in_launch_only:
+                raise RuntimeError("weight EMA: no update is taken in the backward")
             pack_only = self._master_in_backward()
             exclude = self._fused_in_backward() | pack_only
         items, n_items, descs = self._work_table(params, exclude, pack_only)
@@ -643,9 +851,16 @@ class FusedSGD(torch.optim.SGD):
             if self._guard_dev is not None:
                 self._guard_dev.view(torch.int32)[2] = int(gg["skipped"])
             self._guard_cpu[2] = int(gg["skipped"])
+        if "ema_decay" in saved:
+            # the EMA is switched on with the saved decay and seeded from the masters as they
+            # are; its contents travel in the checkpoint (utils/misc.py ``ema_state_dict``)
+            self.set_ema(saved["ema_decay"])
         if not self._fused:
-            return super().load_state_dict({k: v for k, v in sd.items()
-                                            if k not in ("lr_schedule", "grad_guard")})
+            out = super().load_state_dict({k: v for k, v in sd.items()
+                                           if k not in ("lr_schedule", "grad_guard")})
+            if self._ema_decay is not None:  # (an EMA that the saved groups do not know stays on)
+                self.param_groups[0]["ema_decay"] = self._ema_decay
+            return out
         a = self.arena
         st = sd.get("state", {})
         for i, p in enumerate(a.params):

@@ -21,7 +21,7 @@ it per bucket on the comm stream. CPU (Gloo): the same sequence with torch.distr
 """
 import torch
 
-from ..optim.sgd import FusedSGD
+from ..optim.sgd import FusedSGD, _EMA_SHARDED
 
 
 class ShardedUpdate:
@@ -36,6 +36,8 @@ class ShardedUpdate:
         if getattr(optimizer, "needs_whole_tensors", False):
             raise ValueError(f"{type(optimizer).__name__} needs whole tensors: a sharded update "
                              "splits them across ranks; use update=\"allreduce\"")
+        if getattr(optimizer, "updates_in_launch_only", False):
+            raise ValueError(_EMA_SHARDED)
         self.arena, self.opt, self.comm = arena, optimizer, comm
         self.world, self.rank = comm.world, comm.rank
         self.buckets = [tuple(map(tuple, b)) for b in buckets]
@@ -208,6 +210,8 @@ class ShardedBf16Update:
         if getattr(optimizer, "needs_whole_tensors", False):
             raise ValueError(f"{type(optimizer).__name__} needs whole tensors: a sharded update "
                              "splits them across ranks; use update=\"allreduce\"")
+        if getattr(optimizer, "updates_in_launch_only", False):
+            raise ValueError(_EMA_SHARDED)
         self.arena, self.opt, self.comm = arena, optimizer, comm
         self.cuda = arena.data.is_cuda
         self.rank = comm.rank

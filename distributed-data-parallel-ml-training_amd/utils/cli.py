@@ -97,7 +97,19 @@ def build_parser(description=None, distributed=True):
                         'Beta(A, A), one draw per batch from a per-epoch table, inside the batch '
                         'kernel, and the loss is lam * CE(y) + (1 - lam) * CE(y reversed) (works '
                         'inside --graph); default 0 = off')
+    g.add_argument('--ema-decay', type=_ema_decay, default=0.0,
+                   help='exponential moving average of the weights with this decay, 0 <= D < 1, '
+                        'advanced once per optimizer step inside the update launch (works inside '
+                        '--graph); a second evaluation pass runs on the averaged weights and '
+                        '--save stores them as ema_state_dict; default 0 = off')
     return p
+
+
+def _ema_decay(v):
+    d = float(v)
+    if not 0.0 <= d < 1.0:
+        raise argparse.ArgumentTypeError("--ema-decay must be in [0, 1)")
+    return d
 
 
 def _label_smoothing(v):

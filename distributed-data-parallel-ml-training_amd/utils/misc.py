@@ -76,6 +76,9 @@ def save_checkpoint(path, model, optimizer=None, extra=None):
     obj = {"model": sd}
     if optimizer is not None:
         obj["optimizer"] = optimizer.state_dict()
+        if getattr(optimizer, "ema_decay", None) is not None:
+            # the weight EMA (optim/sgd.py set_ema) under the weights' own keys
+            obj["ema_state_dict"] = optimizer.ema_state(m)
     if extra:
         obj["extra"] = extra
     tmp = path + ".tmp"
@@ -83,7 +86,10 @@ def save_checkpoint(path, model, optimizer=None, extra=None):
     os.replace(tmp, path)
 
 
-def load_checkpoint(path, model, optimizer=None, map_location="cpu"):
+def load_checkpoint(path, model, optimizer=None, map_location="cpu", ema_decay=None):
+    """``ema_decay``: switch the optimizer's weight EMA on with this decay once the weights are
+    loaded. An EMA that is on then (by ``ema_decay`` or by the saved optimizer state) takes the
+    checkpoint's ``ema_state_dict``; a checkpoint without one seeds it from the loaded weights."""
     obj = torch.load(path, map_location=map_location, weights_only=True)
     sd = obj["model"] if isinstance(obj, dict) and "model" in obj else obj
     m = model.module if hasattr(model, "module") else model
@@ -94,6 +100,12 @@ def load_checkpoint(path, model, optimizer=None, map_location="cpu"):
         arena.relink()
     if optimizer is not None and isinstance(obj, dict) and "optimizer" in obj:
         optimizer.load_state_dict(obj["optimizer"])
+    if optimizer is not None and hasattr(optimizer, "set_ema"):
+        decay = ema_decay if ema_decay is not None else optimizer.ema_decay
+        if decay is not None:
+            optimizer.set_ema(decay)  # seeded from the loaded weights
+            if isinstance(obj, dict) and "ema_state_dict" in obj:
+                optimizer.load_ema_state(_strip(obj["ema_state_dict"]), m)
     return obj.get("extra") if isinstance(obj, dict) else None
 
 

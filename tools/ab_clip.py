@@ -30,8 +30,8 @@ ARMS = ("sgd_nobwd", "clip_never", "clip_always")
 # (the synthetic set is memorised within a few hundred steps and the gradient norm falls by
 # orders of magnitude: "always" has to stay below any norm the run can reach)
 NEVER, ALWAYS = 1e30, 1e-12
-# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD>, and the sum-of-squares launch
-UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false)>")
+# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD, EMA>, and the sum-of-squares launch
+UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false), (true|false)>")
 SUMSQ = "chunk_sums_kernel<false>"
 
 
@@ -51,7 +51,7 @@ def summarise(prefix):
     for name, n, k in runs:
         if k >= 5:
             print(f"  {name}: {n} x {k}")
-    for key in (SUMSQ, "sgd_pack_kernel<false, true>", "sgd_pack_kernel<false, false>"):
+    for key in (SUMSQ, "sgd_pack_kernel<false, true, false>", "sgd_pack_kernel<false, false, false>"):
         rows = [r for r in trace if key in r["Kernel_Name"]]
         if rows:
             us = sorted((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows)
