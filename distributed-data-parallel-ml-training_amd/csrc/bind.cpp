@@ -587,7 +587,9 @@ PYBIND11_MODULE(_native, m) {
                        uintptr_t lars_tensors, uintptr_t lars_partial, uintptr_t lars_trust,
                        float lars_eta, float lars_eps, uintptr_t clip_partial, int clip_chunks,
                        float clip_max_norm, float clip_eps, int clip_flags,
-                       uintptr_t clip_stats, uintptr_t ema, float ema_one_minus_decay) {
+                       uintptr_t clip_stats, uintptr_t ema, float ema_one_minus_decay,
+                       uintptr_t adam_v, uintptr_t adam_bias, unsigned adam_n_bias,
+                       float adam_omb1, float adam_beta2, float adam_omb2, float adam_eps) {
     ddp_amd::UpdateLaunch u{};
     u.items = P<int4>(items); u.descs = P<ddp_amd::ConvDesc>(descs);
     u.p = P<float>(p); u.g = P<float>(g); u.buf = P<float>(buf);
@@ -600,6 +602,8 @@ PYBIND11_MODULE(_native, m) {
     u.clip = {P<const float>(clip_partial), clip_chunks, clip_max_norm, clip_eps, clip_flags,
               P<float>(clip_stats)};
     u.ema = {P<float>(ema), ema_one_minus_decay};
+    u.adam = {P<float>(adam_v), P<const float2>(adam_bias), adam_n_bias, adam_omb1, adam_beta2,
+              adam_omb2, adam_eps};
     check(ddp_sgd_pack(&u, S(st)), "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
@@ -610,7 +614,10 @@ PYBIND11_MODULE(_native, m) {
      py::arg("lars_partial") = 0, py::arg("lars_trust") = 0, py::arg("lars_eta") = 0.f,
      py::arg("lars_eps") = 0.f, py::arg("clip_partial") = 0, py::arg("clip_chunks") = 0,
      py::arg("clip_max_norm") = 0.f, py::arg("clip_eps") = 0.f, py::arg("clip_flags") = 0,
-     py::arg("clip_stats") = 0, py::arg("ema") = 0, py::arg("ema_one_minus_decay") = 0.f);
+     py::arg("clip_stats") = 0, py::arg("ema") = 0, py::arg("ema_one_minus_decay") = 0.f,
+     py::arg("adam_v") = 0, py::arg("adam_bias") = 0, py::arg("adam_n_bias") = 0,
+     py::arg("adam_omb1") = 0.f, py::arg("adam_beta2") = 0.f, py::arg("adam_omb2") = 0.f,
+     py::arg("adam_eps") = 0.f);
   // gradient guard (optim.hip chunk_sums_kernel<false>): per-chunk sum (g * grad_scale)^2 of every
   // parameter chunk in the items, the input of sgd_pack's clip_* arguments
   m.def("grad_sumsq", [](uintptr_t items, int n_items, uintptr_t g, float grad_scale,

@@ -287,6 +287,26 @@ struct EmaArgs {
   float one_minus_decay;  // float32(1 - decay), rounded once on the host
 };
 
+// AdamW (optim/adamw.py; Loshchilov & Hutter 2019, torch.optim.AdamW with amsgrad=False): ``v``
+// non-null selects the ADAM instantiations, which replace the SGD rule per element, all fp32
+// (``gs`` = grad_scale, times the clip coefficient under the guard):
+//     G   = g * gs
+//     m'  = fma(omb1, G - m, m)                     m: the momentum arena (UpdateLaunch::buf)
+//     v'  = fma(omb2 * G, G, beta2 * v)             v: an arena with the masters' element index
+//     den = fma(sqrt(v'), a2, eps)
+//     u   = m' / den
+//     p'  = fma(-(lr * a1), u, fma(-(lr * wd), p, p))
+// {a1, a2} = {1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} of step t = LrSched::step + 1 come from
+// ``bias``, entry min(step, n_bias - 1): a captured step bakes float arguments in, so they are
+// READ, with the learning rate, once per block. The launch needs SgdHyper::sched (else -1);
+// SgdHyper::momentum and nesterov are unused. Not with LARS, and no item of kind 3.
+struct AdamArgs {
+  float* v;
+  const float2* bias;  // per step: {a1, a2}, computed in fp64 and rounded once on the host
+  unsigned n_bias;     // entries (>= 1); the last one holds for every later step
+  float omb1, beta2, omb2, eps;  // omb1 = float32(1 - beta1), omb2 = float32(1 - beta2)
+};
+
 struct UpdateLaunch {
   const int4* items;      // work items, kinds 0-5 (optim.hip), one block each
   int n_items;
@@ -298,6 +318,7 @@ struct UpdateLaunch {
   LarsArgs lars;          // optional: lars.side == null
   ClipArgs clip;          // optional: clip.partial == null
   EmaArgs ema;            // optional: ema.ema == null
+  AdamArgs adam;          // optional: adam.v == null
 };
 
 struct AugArgs {
@@ -473,7 +494,8 @@ void ddp_conv_force_tile(int tile_plus_one, int stages);
 void ddp_conv_stamps_set(void* buf, int cap);
 #endif
 int ddp_pack_conv_weights(const ddp_amd::PackDesc* descs, int n, hipStream_t st);
-// the fused SGD + re-pack launch (UpdateLaunch above); -1: a LARS pointer or clip.stats missing
+// the fused SGD + re-pack launch (UpdateLaunch above); -1: a LARS pointer or clip.stats missing,
+// or AdamW with LARS, without its bias table or without a schedule
 int ddp_sgd_pack(const ddp_amd::UpdateLaunch* u, hipStream_t st);
 // the two per-chunk sums: int4 items {arena offset, count <= 8192, global chunk, -}, one block
 // each; ``partial`` as ClipArgs::partial (float) and LarsArgs::partial (float2)

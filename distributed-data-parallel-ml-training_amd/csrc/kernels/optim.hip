@@ -7,6 +7,9 @@
 //     p -= lr * d
 // A zero-initialised momentum buffer reproduces torch's "buf = clone(d) on the first step"
 // exactly (momentum * 0 + d == d), so the kernel needs no first-step flag (graph friendly).
+// With AdamW (optim/adamw.py, api.h AdamArgs) the same launch applies Adam with decoupled weight
+// decay instead: the momentum arena holds the first moment, one more arena the second, and the
+// bias corrections of the step come from a device table next to the learning rate's.
 //
 // pack_conv_weights re-lays the fp32 master weights (PyTorch [K][C][R][S]) into the two bf16
 // MFMA operand layouts used by conv_igemm.hip: Wc [K][R][S][Cpad] (fwd) and Wt [C][R][S][K]
@@ -92,7 +95,8 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 // ---------------------------------------------------------------------------------------------
 // Fused SGD + weight re-pack: ONE launch updates the whole arena and writes the bf16 MFMA
 // operand copies of every conv weight from the freshly updated values (no second pass over the
-// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD, EMA>, one block per work item (int4):
+// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD, EMA, ADAM>, one block per work item
+// (int4; "SGD" below is the launch's element rule, AdamW's under ADAM):
 //   {0, offset, count, -}        plain elementwise chunk;
 //   {2, rel_offset, count, desc} elementwise chunk of a conv weight stored [K][R][S][C] (the GPU
 //                                arena layout, C == Cr, or 1x1): its bf16 copy Wc has the same
@@ -106,12 +110,13 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 //                                master + momentum, bf16 operand image of the new values
 //                                (``shadow``), fp32 send slot of the small tensors (offset, count
 //                                and slot_offset multiples of 4: 64-aligned tensors, shards of
-//                                n/w with n % 64 == 0 and w | 8);
+//                                n/w with n % 64 == 0 and w | 8); compiled out under ADAM;
 //   {4, offset, count, -}        clear gradients outside this rank's shard (count multiple of 4);
 //   {5, rel_offset, count, desc} operand re-pack only — the fp32 master was already updated by
 //                                the backward (conv_igemm.hip ConvArgs::sgd); bf16(p) into the
 //                                operand copy (as item 2).
-// Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs, EmaArgs.
+// Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs, EmaArgs,
+// AdamArgs.
 constexpr int kTileElems = 9216;  // fp32 LDS tile (36 KB)
 
 __host__ __device__ __forceinline__ void tile_dims(int RS, int* TK, int* TC) {
@@ -163,9 +168,30 @@ __device__ __forceinline__ void sched_stage(LrSched* s) {
 // plain instantiation compiles to what it was before LARS existed). LARS = true: the same fma
 // chain with the weight-decayed gradient multiplied by the tensor's trust ratio first (a ratio
 // of exactly 1.0 reproduces the plain update bit for bit).
-template <bool LARS>
-__device__ __forceinline__ float sgd1(float p, float g, float& b, const SgdHyper& h, float trust) {
-  if constexpr (!LARS) {
+//
+// ADAM = true: the AdamW rule of api.h AdamArgs on (p, g, m = b, v) with this block's AdamRule.
+// sqrtf and / are correctly rounded: hipcc's default for fp32 (the build passes no -ffast-math
+// and leaves -fhip-fp32-correctly-rounded-divide-sqrt on; tests/test_gpu_adamw_exact.py fails
+// the day that is not so). ``v`` is unread and unwritten without ADAM.
+struct NoAdam {};
+struct AdamRule {
+  float nla, nlw;  // -(lr * a1), -(lr * wd): one fp32 product each, once per block
+  float a2, eps, omb1, beta2, omb2;
+};
+template <bool ADAM>
+using RuleOf = std::conditional_t<ADAM, AdamRule, NoAdam>;
+
+template <bool LARS, bool ADAM>
+__device__ __forceinline__ float sgd1(float p, float g, float& b, float& v, const SgdHyper& h,
+                                      float trust, const RuleOf<ADAM>& r) {
+  if constexpr (ADAM) {
+    const float G = g * h.grad_scale;
+    b = __builtin_fmaf(r.omb1, G - b, b);
+    v = __builtin_fmaf(r.omb2 * G, G, r.beta2 * v);
+    const float den = __builtin_fmaf(sqrtf(v), r.a2, r.eps);
+    const float u = b / den;
+    return __builtin_fmaf(r.nla, u, __builtin_fmaf(r.nlw, p, p));
+  } else if constexpr (!LARS) {
     return sgd_update1(p, g, b, h.lr, h.momentum, h.wd, h.grad_scale, h.nesterov);
   } else {
     float d = trust * __builtin_fmaf(h.wd, p, g * h.grad_scale);
@@ -202,22 +228,53 @@ __device__ __forceinline__ float* ema_at(const EmaOf<EMA>& m, size_t i) {
   else return nullptr;
 }
 
-// The update of four elements (16-byte aligned) on float4 registers: p and buf stored, +0 into
-// g under zero_grad, the EMA of the four (``e``: ema_at of the same index); returns the new p.
-template <bool LARS, bool EMA>
-__device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, const SgdHyper& h,
-                                       float trust, float* e, const EmaOf<EMA>& m) {
+// The second moment's element of arena index i (``v`` is null without ADAM: never read).
+template <bool ADAM>
+__device__ __forceinline__ float* v_at(float* v, size_t i) {
+  if constexpr (ADAM) return v + i;
+  else return nullptr;
+}
+
+// One element by its arena index, every path that is not 16 bytes wide: p, buf (and v) stored,
+// +0 into g under zero_grad, the EMA; returns the new p.
+template <bool LARS, bool EMA, bool ADAM>
+__device__ __forceinline__ float update1(float* __restrict__ p, float* __restrict__ g,
+                                         float* __restrict__ buf, float* v, size_t i,
+                                         const SgdHyper& h, float trust, const EmaOf<EMA>& m,
+                                         const RuleOf<ADAM>& r) {
+  float b = buf[i];
+  float vv = 0.f;  // (unused without ADAM)
+  if constexpr (ADAM) vv = v[i];
+  const float np = sgd1<LARS, ADAM>(p[i], g[i], b, vv, h, trust, r);
+  p[i] = np;
+  buf[i] = b;
+  if constexpr (ADAM) v[i] = vv;
+  if (h.zero_grad) g[i] = 0.f;
+  ema1<EMA>(m, i, np);  // (the arena index, as p: the EMA has the masters' layout)
+  return np;
+}
+
+// The update of four elements (16-byte aligned) on float4 registers: p and buf (and v: v_at of
+// the same index) stored, +0 into g under zero_grad, the EMA of the four (``e``: ema_at of the
+// same index); returns the new p.
+template <bool LARS, bool EMA, bool ADAM>
+__device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, float* v,
+                                       const SgdHyper& h, float trust, float* e,
+                                       const EmaOf<EMA>& m, const RuleOf<ADAM>& r) {
   float4 pv = *reinterpret_cast<float4*>(p);
   const float4 gv = *reinterpret_cast<const float4*>(g);
   float4 bv = *reinterpret_cast<float4*>(buf);
+  float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);  // (unused without ADAM)
+  if constexpr (ADAM) vv = *reinterpret_cast<const float4*>(v);
   float4 ev;  // (unused without EMA)
   if constexpr (EMA) ev = *reinterpret_cast<const float4*>(e);
-  pv.x = sgd1<LARS>(pv.x, gv.x, bv.x, h, trust);
-  pv.y = sgd1<LARS>(pv.y, gv.y, bv.y, h, trust);
-  pv.z = sgd1<LARS>(pv.z, gv.z, bv.z, h, trust);
-  pv.w = sgd1<LARS>(pv.w, gv.w, bv.w, h, trust);
+  pv.x = sgd1<LARS, ADAM>(pv.x, gv.x, bv.x, vv.x, h, trust, r);
+  pv.y = sgd1<LARS, ADAM>(pv.y, gv.y, bv.y, vv.y, h, trust, r);
+  pv.z = sgd1<LARS, ADAM>(pv.z, gv.z, bv.z, vv.z, h, trust, r);
+  pv.w = sgd1<LARS, ADAM>(pv.w, gv.w, bv.w, vv.w, h, trust, r);
   *reinterpret_cast<float4*>(p) = pv;
   *reinterpret_cast<float4*>(buf) = bv;
+  if constexpr (ADAM) *reinterpret_cast<float4*>(v) = vv;
   if (h.zero_grad) *reinterpret_cast<float4*>(g) = make_float4(0.f, 0.f, 0.f, 0.f);
   if constexpr (EMA) {
     ev.x = ema_lerp(ev.x, pv.x, m.one_minus_decay);
@@ -452,13 +509,14 @@ __device__ __forceinline__ void guard_clear(const int4& it, const ConvDesc* __re
   for (int i = threadIdx.x; i < it.z; i += 256) gp[i] = 0.f;
 }
 
-template <bool LARS, bool GUARD, bool EMA>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM>
 __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
                                               const ConvDesc* __restrict__ descs,
                                               float* __restrict__ p, float* __restrict__ g,
                                               float* __restrict__ buf, const SgdHyper& h,
                                               float* tile, float trust, const GuardState& gd,
-                                              const EmaOf<EMA>& m) {
+                                              const EmaOf<EMA>& m, float* v,
+                                              const RuleOf<ADAM>& r) {
   const int4 it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
@@ -483,29 +541,25 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t off = elem_offset(it, descs);
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
         if (i + 4 <= cnt && ((off + i) & 3) == 0) {
-          sgd4<LARS, EMA>(p + off + i, g + off + i, buf + off + i, h, trust,
-                          ema_at<EMA>(m, off + i), m);
+          sgd4<LARS, EMA, ADAM>(p + off + i, g + off + i, buf + off + i, v_at<ADAM>(v, off + i),
+                                h, trust, ema_at<EMA>(m, off + i), m, r);
         } else {
-          for (int e = i; e < min(cnt, i + 4); ++e) {
-            float b = buf[off + e];
-            const float np = sgd1<LARS>(p[off + e], g[off + e], b, h, trust);
-            p[off + e] = np;
-            buf[off + e] = b;
-            if (h.zero_grad) g[off + e] = 0.f;
-            ema1<EMA>(m, off + e, np);
-          }
+          for (int e = i; e < min(cnt, i + 4); ++e)
+            update1<LARS, EMA, ADAM>(p, g, buf, v, off + e, h, trust, m, r);
         }
       }
       break;
     }
     case 3: {
-      const size_t off = elem_offset(it, descs);
-      float* slot = it.w >= 0 && h.slot ? h.slot + it.w : nullptr;
-      for (int i = tid * 4; i < cnt; i += 256 * 4) {
-        const float4 pv = sgd4<LARS, EMA>(p + off + i, g + off + i, buf + off + i, h, trust,
-                                          ema_at<EMA>(m, off + i), m);
-        if (h.shadow) *reinterpret_cast<uint2*>(h.shadow + off + i) = bf16x4(pv);
-        if (slot) *reinterpret_cast<float4*>(slot + i) = pv;
+      if constexpr (!ADAM) {  // (no sharded AdamW: optim/adamw.py refuses before such a table)
+        const size_t off = elem_offset(it, descs);
+        float* slot = it.w >= 0 && h.slot ? h.slot + it.w : nullptr;
+        for (int i = tid * 4; i < cnt; i += 256 * 4) {
+          const float4 pv = sgd4<LARS, EMA, ADAM>(p + off + i, g + off + i, buf + off + i, nullptr,
+                                                  h, trust, ema_at<EMA>(m, off + i), m, r);
+          if (h.shadow) *reinterpret_cast<uint2*>(h.shadow + off + i) = bf16x4(pv);
+          if (slot) *reinterpret_cast<float4*>(slot + i) = pv;
+        }
       }
       break;
     }
@@ -519,8 +573,9 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t base = elem_offset(it, descs);
       unsigned short* wc = descs[it.w].wc + (unsigned)it.y;
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
-        const float4 pv = sgd4<LARS, EMA>(p + base + i, g + base + i, buf + base + i, h, trust,
-                                          ema_at<EMA>(m, base + i), m);
+        const float4 pv = sgd4<LARS, EMA, ADAM>(p + base + i, g + base + i, buf + base + i,
+                                                v_at<ADAM>(v, base + i), h, trust,
+                                                ema_at<EMA>(m, base + i), m, r);
         *reinterpret_cast<uint2*>(wc + i) = bf16x4(pv);
       }
       break;
@@ -537,13 +592,7 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const Tile t(d, it);
       // 1) SGD on the master for the tile's real channels, new values into the LDS tile
       t.for_each_master([&](size_t gi, int li) {
-        float b = buf[gi];
-        const float np = sgd1<LARS>(p[gi], g[gi], b, h, trust);
-        p[gi] = np;
-        buf[gi] = b;
-        if (h.zero_grad) g[gi] = 0.f;
-        ema1<EMA>(m, gi, np);  // (the arena index, as p: the EMA has the masters' layout)
-        tile[li] = np;
+        tile[li] = update1<LARS, EMA, ADAM>(p, g, buf, v, gi, h, trust, m, r);
       });
       __syncthreads();
       // 2) Wc[k][r][s][c] (c fastest, zero for padded channels)
@@ -569,33 +618,65 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
 }
 
 // The kernel's arguments behind the tables and arenas (their __restrict__ keeps the table reads
-// scalar): SgdHyper, then LarsArgs, ClipArgs and EmaArgs only in the instantiations that read
-// them (an empty base takes no kernarg bytes; an empty struct argument would).
+// scalar): SgdHyper, then LarsArgs, ClipArgs, EmaArgs and AdamArgs only in the instantiations
+// that read them (an empty base takes no kernarg bytes; an empty struct argument would).
 struct NoLars {};
 struct NoClip {};
-template <bool LARS, bool GUARD, bool EMA>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM>
 struct UpdateArgs : SgdHyper, std::conditional_t<LARS, LarsArgs, NoLars>,
-                    std::conditional_t<GUARD, ClipArgs, NoClip>, EmaOf<EMA> {};
-static_assert(sizeof(UpdateArgs<false, false, false>) == 96 &&
-              sizeof(UpdateArgs<false, true, false>) == 128 &&
-              sizeof(UpdateArgs<true, false, false>) == 136 &&
-              sizeof(UpdateArgs<true, true, false>) == 168 &&
-              sizeof(UpdateArgs<false, false, true>) == 112 &&
-              sizeof(UpdateArgs<false, true, true>) == 144 &&
-              sizeof(UpdateArgs<true, false, true>) == 152 &&
-              sizeof(UpdateArgs<true, true, true>) == 184,
-              "kernarg bytes of the eight instantiations");
+                    std::conditional_t<GUARD, ClipArgs, NoClip>, EmaOf<EMA>,
+                    std::conditional_t<ADAM, AdamArgs, NoAdam> {};
+static_assert(sizeof(UpdateArgs<false, false, false, false>) == 96 &&
+              sizeof(UpdateArgs<false, true, false, false>) == 128 &&
+              sizeof(UpdateArgs<true, false, false, false>) == 136 &&
+              sizeof(UpdateArgs<true, true, false, false>) == 168 &&
+              sizeof(UpdateArgs<false, false, true, false>) == 112 &&
+              sizeof(UpdateArgs<false, true, true, false>) == 144 &&
+              sizeof(UpdateArgs<true, false, true, false>) == 152 &&
+              sizeof(UpdateArgs<true, true, true, false>) == 184 &&
+              sizeof(UpdateArgs<false, false, false, true>) == 136 &&
+              sizeof(UpdateArgs<false, true, false, true>) == 168 &&
+              sizeof(UpdateArgs<false, false, true, true>) == 152 &&
+              sizeof(UpdateArgs<false, true, true, true>) == 184,
+              "kernarg bytes of the twelve instantiations (ADAM excludes LARS)");
 
-template <bool LARS, bool GUARD, bool EMA>
+// ADAM: this step's {learning rate, a1, a2} (api.h AdamArgs), read once per block where the plain
+// instantiations read the learning rate: thread 0 loads, LDS broadcast, one barrier. The step
+// word is the schedule's (common.h sched_lr): no launch that reads it writes it.
+__device__ __forceinline__ AdamRule adam_rule_block(const AdamArgs& a, const SgdHyper& h) {
+  __shared__ float s_rule[3];
+  if (threadIdx.x == 0) {
+    const LrSched* s = h.sched;
+    const unsigned k = __hip_atomic_load(&s->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned n = s->n;
+    const float lr = reinterpret_cast<const float*>(s + 1)[k < n ? k : n - 1];
+    const float2 bc = a.bias[k < a.n_bias ? k : a.n_bias - 1];
+    s_rule[0] = -(lr * bc.x);
+    s_rule[1] = -(lr * h.wd);
+    s_rule[2] = bc.y;
+  }
+  __syncthreads();
+  return AdamRule{s_rule[0], s_rule[1], s_rule[2], a.eps, a.omb1, a.beta2, a.omb2};
+}
+
+template <bool LARS, bool GUARD, bool EMA, bool ADAM>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
                                                        const ConvDesc* __restrict__ descs,
                                                        float* __restrict__ p,
                                                        float* __restrict__ g,
                                                        float* __restrict__ buf,
-                                                       UpdateArgs<LARS, GUARD, EMA> a) {
+                                                       UpdateArgs<LARS, GUARD, EMA, ADAM> a) {
+  static_assert(!(LARS && ADAM), "AdamW has no trust ratios");
   __shared__ float tile[kTileElems];
   SgdHyper h = a;
-  h.lr = sched_lr_block(h.sched, h.lr);
+  RuleOf<ADAM> rule{};
+  float* v = nullptr;  // (stays null and unread without ADAM)
+  if constexpr (ADAM) {
+    rule = adam_rule_block(a, h);
+    v = a.v;
+  } else {
+    h.lr = sched_lr_block(h.sched, h.lr);
+  }
   if (h.sched_advance && blockIdx.x == 0 && threadIdx.x == 0) sched_stage(h.sched);
   GuardState gd{0.f, 1.f, 0, nullptr, 0};
   if constexpr (GUARD) gd = clip_block(a);
@@ -603,7 +684,7 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
   // (a skipped step leaves the stored ratios as they are)
   if constexpr (LARS) trust = GUARD && gd.skipped ? 1.f : lars_trust_block<GUARD>(a, h.wd, gd.c);
   if constexpr (GUARD) h.grad_scale *= gd.c;
-  sgd_pack_body<LARS, GUARD, EMA>(items, descs, p, g, buf, h, tile, trust, gd, a);
+  sgd_pack_body<LARS, GUARD, EMA, ADAM>(items, descs, p, g, buf, h, tile, trust, gd, a, v, rule);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
@@ -657,15 +738,16 @@ __global__ void counter_add_kernel(int* c, int delta, LrSched* sched, int sched_
   __hip_atomic_store(&sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool LARS, bool GUARD, bool EMA>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM = false>
 static int launch_update(const UpdateLaunch& u, hipStream_t st) {
-  UpdateArgs<LARS, GUARD, EMA> a{};
+  UpdateArgs<LARS, GUARD, EMA, ADAM> a{};
   static_cast<SgdHyper&>(a) = u.h;
   a.sched_advance = a.sched && a.sched_advance ? 1 : 0;
   if constexpr (LARS) static_cast<LarsArgs&>(a) = u.lars;
   if constexpr (GUARD) static_cast<ClipArgs&>(a) = u.clip;
   if constexpr (EMA) static_cast<EmaArgs&>(a) = u.ema;
-  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA>), dim3(u.n_items), dim3(256), 0, st, u.items,
+  if constexpr (ADAM) static_cast<AdamArgs&>(a) = u.adam;
+  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA, ADAM>), dim3(u.n_items), dim3(256), 0, st, u.items,
                      u.descs, u.p, u.g, u.buf, a);
   return (int)hipGetLastError();
 }
@@ -718,6 +800,14 @@ extern "C" int ddp_sgd_pack(const UpdateLaunch* u, hipStream_t st) {
   const bool lars = u->lars.side, guard = u->clip.partial;
   if (guard && (!u->clip.stats || u->clip.n_chunks < 0)) return -1;
   if (lars && (!u->lars.tensors || !u->lars.partial || !u->lars.trust)) return -1;
+  if (u->adam.v) {  // AdamW: the step number comes from the schedule's step word
+    if (lars || !u->adam.bias || !u->adam.n_bias || !u->h.sched) return -1;
+    if (u->ema.ema)
+      return (guard ? launch_update<false, true, true, true>
+                    : launch_update<false, false, true, true>)(*u, st);
+    return (guard ? launch_update<false, true, false, true>
+                  : launch_update<false, false, false, true>)(*u, st);
+  }
   if (u->ema.ema)
     return (lars ? (guard ? launch_update<true, true, true> : launch_update<true, false, true>)
                  : (guard ? launch_update<false, true, true> : launch_update<false, false, true>))(*u, st);

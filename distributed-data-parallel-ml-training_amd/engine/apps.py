@@ -63,7 +63,7 @@ def main(part, argv=None):
                                         captured=captured)
     # --lr / --lr-schedule ... (opt-in; default: the reference's constant 0.1, nothing attached)
     lr, schedule = lr_schedule_from_args(args, len(train_loader))
-    optimizer = optimizer_from_args(args, model.parameters(), lr)  # --optimizer sgd | lars
+    optimizer = optimizer_from_args(args, model.parameters(), lr)  # --optimizer sgd | lars | adamw
     if schedule is not None:
         optimizer.set_schedule(schedule)
     # --ema-decay (opt-in): the average starts as a copy of the weights, so it is switched on
@@ -95,8 +95,7 @@ def main(part, argv=None):
         # it back after the capture, so the epoch starts exactly where the eager loop would
         from .step import TrainStep, SegmentedDDPStep, default_cuts
         arena = model.arena if hasattr(model, "arena") else optimizer.arena
-        snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), optimizer.lr_step,
-                optimizer.ema.clone() if ema_on else None)
+        snap = (arena.data.clone(), optimizer.state_snapshot())
         split = [int(v) for v in os.environ.get("DDP_AMD_SEGMENTED",
                                                 default_cuts(args.model, batch_size)).split(",")
                  if int(v) > 0]
@@ -117,10 +116,9 @@ def main(part, argv=None):
                   flush=True)
         torch.cuda.synchronize()
         arena.data.copy_(snap[0])
-        optimizer.momentum_buffer.copy_(snap[1])
-        optimizer.set_lr_step(snap[2])  # the warm-up / validation steps used no schedule entry
-        if ema_on:
-            optimizer.ema.copy_(snap[3])  # ... and averaged nothing
+        # momentum (and AdamW's second moment); the warm-up / validation steps used no schedule
+        # entry and averaged nothing
+        optimizer.restore_state(snap[1])
         optimizer.repack()
         train_loader.cursor.zero_()
         del snap

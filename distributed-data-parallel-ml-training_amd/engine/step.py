@@ -94,7 +94,8 @@ class TrainStep:
         # finish that completes its gradient; the step's SGD launch covers only the rest
         # (optim/sgd.py register_in_backward). DDP_AMD_SGD_IN_BWD=0 keeps the separate pass.
         # LARS needs the norm of the whole gradient before any element moves: never in the backward.
-        # The weight EMA is advanced by the step's update launch: every update runs there.
+        # The weight EMA is advanced by the step's update launch, and AdamW's rule exists there
+        # only: every update runs there.
         self.opt_in_bwd = (self.fold_opt and sync is None and sgd_in_backward_ok(model)
                            and hasattr(optimizer, "register_in_backward")
                            and not getattr(optimizer, "needs_whole_tensors", False)
@@ -440,10 +441,11 @@ class SegmentedDDPStep(TrainStep):
                              + ": the sharded updates (zero=True, \"s16\" buckets) split them "
                              "across ranks; use update=\"allreduce\"")
         if getattr(optimizer, "updates_in_launch_only", False) and (zero or "s16" in update):
-            # the weight EMA is taken in the replicated update launches: each bucket's launch
-            # carries it for its own items, the guard's whole-arena launch for all of them
-            raise ValueError(f"{type(optimizer).__name__} with a weight EMA: the sharded updates "
-                             "(zero=True, \"s16\" buckets) do not advance it; use "
+            # the weight EMA is taken, and AdamW's rule exists, in the replicated update launches
+            # only: each bucket's launch runs them for its own items, the guard's whole-arena
+            # launch for all of them
+            raise ValueError(f"{type(optimizer).__name__}: {optimizer.launch_only_reason}; the "
+                             "sharded updates (zero=True, \"s16\" buckets) do not carry it; use "
                              "update=\"allreduce\"")
         self.zero = None
         self.shard16 = None
@@ -738,9 +740,8 @@ def profile_stage_times(ddp, optimizer, criterion, loader, n_stages, reps=4):
     from the same state on every rank. Returns a list of n_stages floats (us, median over reps). Feeds
     parallel/cut_plan.plan_cuts."""
     arena = ddp.arena
-    snap = (arena.data.clone(), optimizer.momentum_buffer.clone(), loader.cursor.clone())
-    ema = optimizer.ema.clone() if getattr(optimizer, "ema_decay", None) is not None else None
-    lr_step = getattr(optimizer, "lr_step", 0)  # the profiled steps must not use the schedule up
+    # (the optimizer's part holds the schedule's step: the profiled steps must not use it up)
+    snap = (arena.data.clone(), optimizer.state_snapshot(), loader.cursor.clone())
     # module buffers too (ResNet's BatchNorm running statistics): the profiling batches must
     # not leave extra updates behind
     bufs = [b for b in ddp.module.buffers()]
@@ -762,12 +763,8 @@ def profile_stage_times(ddp, optimizer, criterion, loader, n_stages, reps=4):
         torch.cuda.synchronize()
         st.graphs = st.graph = None
         arena.data.copy_(snap[0])
-        optimizer.momentum_buffer.copy_(snap[1])
+        optimizer.restore_state(snap[1])
         loader.cursor.copy_(snap[2])
-        if ema is not None:
-            optimizer.ema.copy_(ema)
-        if hasattr(optimizer, "set_lr_step"):
-            optimizer.set_lr_step(lr_step)
         for b, v in zip(bufs, bsnap):
             b.copy_(v)
         arena.grad.zero_()

@@ -78,6 +78,13 @@ def _ema_field(optimizer):
     return {} if d is None else {"ema_decay": d}
 
 
+def _optimizer_field(optimizer):
+    """Extra metrics field of one iteration: the optimizer's name where it is not the reference's
+    SGD family (optim/adamw.py ``metrics_name``; records of sgd and lars runs stay as they were)."""
+    name = getattr(optimizer, "metrics_name", None)
+    return {} if name is None else {"optimizer": name}
+
+
 def micro_batch_ctx(model, first, last):
     """DDP wrapper state of one micro-batch of an accumulated step: no gradient collective
     before the last one (``no_sync``), the buffer broadcast only before the first one."""
@@ -154,6 +161,7 @@ class _Iterations:
             self.metrics.log(event="iter", epoch=self.epoch, batch=it, ns=dt,
                              **({"accum": m} if self.accum else {}), **self.lr,
                              **_guard_stats(self.optimizer), **_ema_field(self.optimizer),
+                             **_optimizer_field(self.optimizer),
                              **({"lam": lam if self.accum else lam[0]} if lam else {}))
         if self.watchdog is not None:
             self.watchdog.beat()

@@ -67,10 +67,17 @@ _GUARD_SHARDED = ("gradient clipping / non-finite step skipping needs the norm o
                   "norm would need one more collective; use the replicated update, "
                   "update=\"allreduce\"")
 _EMA_LAUNCH_ONLY = ("the weight EMA is advanced by the step's own update launch, from the new "
-                    "master in its registers: ")
-_EMA_SHARDED = (_EMA_LAUNCH_ONLY + "the sharded updates (ZeRO-1, the bf16-gather update) and "
-                "element-range updates do not carry it; use the replicated update, "
-                "update=\"allreduce\"")
+                    "master in its registers")
+_SHARDED_LAUNCH_ONLY = ("the sharded updates (ZeRO-1, the bf16-gather update) and element-range "
+                        "updates do not carry it; use the replicated update, update=\"allreduce\"")
+_BWD_LAUNCH_ONLY = ("an update taken in the backward's WGRAD finishes would not carry it "
+                    "(TrainStep keeps opt_in_bwd False)")
+
+
+def launch_only_sharded(optimizer):
+    """The refusal of a sharded or element-range update for an optimizer whose updates run in
+    the step's launch only, naming the reason (the weight EMA, AdamW)."""
+    return optimizer.launch_only_reason + ": " + _SHARDED_LAUNCH_ONLY
 
 
 def one_minus_decay(decay):
@@ -345,11 +352,24 @@ class FusedSGD(torch.optim.SGD):
         """The EMA arena: flat fp32, the masters' element index (None before ``set_ema``)."""
         return self._ema
 
+    # why every update of this optimizer class has to run in the step's own update launch,
+    # whatever its options (optim/adamw.py: the rule exists there only); None: no such reason
+    _rule_launch_only = None
+
+    @property
+    def launch_only_reason(self):
+        """Why every update has to run in the step's own update launch (the optimizer's rule,
+        the weight EMA, or both), or None."""
+        why = [w for w in (self._rule_launch_only,
+                           _EMA_LAUNCH_ONLY if self._ema_decay is not None else None) if w]
+        return "; ".join(why) if why else None
+
     @property
     def updates_in_launch_only(self):
         """Every update of this optimizer has to run in the step's own update launch (the
-        weight EMA is taken there): no SGD in the backward, no sharded or element-range update."""
-        return self._ema_decay is not None
+        weight EMA is taken there, AdamW's rule exists there only): no SGD in the backward, no
+        sharded or element-range update. ``launch_only_reason`` says why."""
+        return self.launch_only_reason is not None
 
     def _ema_kw(self):
         """Extra arguments of a native update launch: none with the EMA off (the launch is then
@@ -489,6 +509,28 @@ class FusedSGD(torch.optim.SGD):
             return
         self._lr_step += 1
 
+    # ------------------------------------------------------------- state snapshot and rollback
+    def _state_arenas(self):
+        """The optimizer's own arenas on the GPU, in snapshot order: momentum (optim/adamw.py
+        adds the second moment)."""
+        return [self.momentum_buffer]
+
+    def state_snapshot(self):
+        """Clones of everything a training step changes in the optimizer (GPU): momentum (and
+        AdamW's second moment), the schedule's step, the weight EMA if it is on. For the
+        roll-backs around warm-up, capture, validation and profiling steps."""
+        return {"arenas": [t.clone() for t in self._state_arenas()], "lr_step": self._lr_step,
+                "ema": self._ema.clone() if self._ema_decay is not None else None}
+
+    @torch.no_grad()
+    def restore_state(self, snap):
+        """Inverse of ``state_snapshot``, in place: addresses stay, captured graphs stay valid."""
+        for t, v in zip(self._state_arenas(), snap["arenas"]):
+            t.copy_(v)
+        self.set_lr_step(snap["lr_step"])
+        if snap["ema"] is not None:
+            self._ema.copy_(snap["ema"])
+
     def _sched_ptr(self):
         return self._lr_dev.data_ptr() if (self._schedule is not None and self._fused) else 0
 
@@ -545,8 +587,7 @@ class FusedSGD(torch.optim.SGD):
                                "backward: the norm exists only once the whole gradient does "
                                "(TrainStep keeps opt_in_bwd False)")
         if self.updates_in_launch_only:
-            raise RuntimeError(_EMA_LAUNCH_ONLY + "an update taken in the backward's WGRAD "
-                               "finishes would not advance it (TrainStep keeps opt_in_bwd False)")
+            raise RuntimeError(self.launch_only_reason + ": " + _BWD_LAUNCH_ONLY)
         from ..ops.common import native
         a, g = self.arena, self.param_groups[0]
         nat = native()
@@ -677,7 +718,7 @@ class FusedSGD(torch.optim.SGD):
         if self.guarded:
             raise ValueError(_GUARD_SHARDED)
         if self.updates_in_launch_only:
-            raise ValueError(_EMA_SHARDED)
+            raise ValueError(launch_only_sharded(self))
         g = self.param_groups[0]
         lr, m, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
         a = self.arena
@@ -802,7 +843,8 @@ class FusedSGD(torch.optim.SGD):
             if self.guarded:
                 raise RuntimeError("gradient guard: no update is taken in the backward")
             if self.updates_in_launch_only:
-                raise RuntimeError("weight EMA: no update is taken in the backward")
+                raise RuntimeError(self.launch_only_reason + ": no update is taken in the "
+                                   "backward")
             pack_only = self._master_in_backward()
             exclude = self._fused_in_backward() | pack_only
         items, n_items, descs = self._work_table(params, exclude, pack_only)

@@ -21,7 +21,7 @@ it per bucket on the comm stream. CPU (Gloo): the same sequence with torch.distr
 """
 import torch
 
-from ..optim.sgd import FusedSGD, _EMA_SHARDED
+from ..optim.sgd import FusedSGD, launch_only_sharded
 
 
 class ShardedUpdate:
@@ -37,7 +37,7 @@ class ShardedUpdate:
             raise ValueError(f"{type(optimizer).__name__} needs whole tensors: a sharded update "
                              "splits them across ranks; use update=\"allreduce\"")
         if getattr(optimizer, "updates_in_launch_only", False):
-            raise ValueError(_EMA_SHARDED)
+            raise ValueError(launch_only_sharded(optimizer))
         self.arena, self.opt, self.comm = arena, optimizer, comm
         self.world, self.rank = comm.world, comm.rank
         self.buckets = [tuple(map(tuple, b)) for b in buckets]
@@ -211,7 +211,7 @@ class ShardedBf16Update:
             raise ValueError(f"{type(optimizer).__name__} needs whole tensors: a sharded update "
                              "splits them across ranks; use update=\"allreduce\"")
         if getattr(optimizer, "updates_in_launch_only", False):
-            raise ValueError(_EMA_SHARDED)
+            raise ValueError(launch_only_sharded(optimizer))
         self.arena, self.opt, self.comm = arena, optimizer, comm
         self.cuda = arena.data.is_cuda
         self.rank = comm.rank

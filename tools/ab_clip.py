@@ -30,8 +30,8 @@ ARMS = ("sgd_nobwd", "clip_never", "clip_always")
 # (the synthetic set is memorised within a few hundred steps and the gradient norm falls by
 # orders of magnitude: "always" has to stay below any norm the run can reach)
 NEVER, ALWAYS = 1e30, 1e-12
-# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD, EMA>, and the sum-of-squares launch
-UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false), (true|false)>")
+# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD, EMA, ADAM>, and the sum-of-squares launch
+UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false), (true|false), (true|false)>")
 SUMSQ = "chunk_sums_kernel<false>"
 
 

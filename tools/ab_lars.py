@@ -25,8 +25,8 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 ARMS = ("sgd", "sgd_nobwd", "lars")
-# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD, EMA>, and the norms launch
-UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false), (true|false)>")
+# the update launch, optim.hip sgd_pack_kernel<LARS, GUARD, EMA, ADAM>, and the norms launch
+UPDATE = re.compile(r"sgd_pack_kernel<(true|false), (true|false), (true|false), (true|false)>")
 NORMS = "chunk_sums_kernel<true>"
 
 
