@@ -589,7 +589,9 @@ PYBIND11_MODULE(_native, m) {
                        float clip_max_norm, float clip_eps, int clip_flags,
                        uintptr_t clip_stats, uintptr_t ema, float ema_one_minus_decay,
                        uintptr_t adam_v, uintptr_t adam_bias, unsigned adam_n_bias,
-                       float adam_omb1, float adam_beta2, float adam_omb2, float adam_eps) {
+                       float adam_omb1, float adam_beta2, float adam_omb2, float adam_eps,
+                       uintptr_t lamb_side, uintptr_t lamb_tensors, uintptr_t lamb_partial,
+                       uintptr_t lamb_trust) {
     ddp_amd::UpdateLaunch u{};
     u.items = P<int4>(items); u.descs = P<ddp_amd::ConvDesc>(descs);
     u.p = P<float>(p); u.g = P<float>(g); u.buf = P<float>(buf);
@@ -604,6 +606,8 @@ PYBIND11_MODULE(_native, m) {
     u.ema = {P<float>(ema), ema_one_minus_decay};
     u.adam = {P<float>(adam_v), P<const float2>(adam_bias), adam_n_bias, adam_omb1, adam_beta2,
               adam_omb2, adam_eps};
+    u.lamb = {P<int2>(lamb_side), P<int4>(lamb_tensors), P<float2>(lamb_partial),
+              P<float>(lamb_trust)};
     check(ddp_sgd_pack(&u, S(st)), "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
@@ -617,7 +621,8 @@ PYBIND11_MODULE(_native, m) {
      py::arg("clip_stats") = 0, py::arg("ema") = 0, py::arg("ema_one_minus_decay") = 0.f,
      py::arg("adam_v") = 0, py::arg("adam_bias") = 0, py::arg("adam_n_bias") = 0,
      py::arg("adam_omb1") = 0.f, py::arg("adam_beta2") = 0.f, py::arg("adam_omb2") = 0.f,
-     py::arg("adam_eps") = 0.f);
+     py::arg("adam_eps") = 0.f, py::arg("lamb_side") = 0, py::arg("lamb_tensors") = 0,
+     py::arg("lamb_partial") = 0, py::arg("lamb_trust") = 0);
   // gradient guard (optim.hip chunk_sums_kernel<false>): per-chunk sum (g * grad_scale)^2 of every
   // parameter chunk in the items, the input of sgd_pack's clip_* arguments
   m.def("grad_sumsq", [](uintptr_t items, int n_items, uintptr_t g, float grad_scale,
@@ -634,6 +639,31 @@ PYBIND11_MODULE(_native, m) {
                          P<void>(partial), S(st)), "lars_norms");
   }, py::arg("items"), py::arg("n_items"), py::arg("p"), py::arg("g"), py::arg("grad_scale"),
      py::arg("partial"), py::arg("stream"));
+  // LAMB norms launch (optim.hip lamb_norms_kernel): per-chunk {sum p^2, sum r^2}, r the update
+  // direction of api.h LambArgs; adam_* as sgd_pack's, clip_* select the guarded instantiation
+  m.def("lamb_norms", [](uintptr_t items, int n_items, uintptr_t p, uintptr_t g, uintptr_t m,
+                         float wd, float grad_scale, uintptr_t partial, uintptr_t st,
+                         uintptr_t sched, uintptr_t adam_v, uintptr_t adam_bias,
+                         unsigned adam_n_bias, float adam_omb1, float adam_beta2, float adam_omb2,
+                         float adam_eps, uintptr_t clip_partial, int clip_chunks,
+                         float clip_max_norm, float clip_eps, int clip_flags) {
+    ddp_amd::LambNorms n{};
+    n.items = P<int4>(items); n.n_items = n_items;
+    n.p = P<float>(p); n.g = P<float>(g); n.m = P<float>(m);
+    n.sched = P<ddp_amd::LrSched>(sched); n.wd = wd; n.grad_scale = grad_scale;
+    n.adam = {P<float>(adam_v), P<const float2>(adam_bias), adam_n_bias, adam_omb1, adam_beta2,
+              adam_omb2, adam_eps};
+    n.partial = P<float2>(partial);
+    n.clip = {P<const float>(clip_partial), clip_chunks, clip_max_norm, clip_eps, clip_flags,
+              nullptr};
+    check(ddp_lamb_norms(&n, S(st)), "lamb_norms");
+  }, py::arg("items"), py::arg("n_items"), py::arg("p"), py::arg("g"), py::arg("m"),
+     py::arg("wd"), py::arg("grad_scale"), py::arg("partial"), py::arg("stream"),
+     py::arg("sched") = 0, py::arg("adam_v") = 0, py::arg("adam_bias") = 0,
+     py::arg("adam_n_bias") = 0, py::arg("adam_omb1") = 0.f, py::arg("adam_beta2") = 0.f,
+     py::arg("adam_omb2") = 0.f, py::arg("adam_eps") = 0.f, py::arg("clip_partial") = 0,
+     py::arg("clip_chunks") = 0, py::arg("clip_max_norm") = 0.f, py::arg("clip_eps") = 0.f,
+     py::arg("clip_flags") = 0);
   m.def("shard_tail", [](uintptr_t segs, int n_segs, uintptr_t src, uintptr_t dst,
                          const std::vector<PackTuple>& descs, uintptr_t done, uintptr_t signal,
                          uintptr_t skip, uintptr_t st) {

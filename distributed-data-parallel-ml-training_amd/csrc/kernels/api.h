@@ -307,6 +307,41 @@ struct AdamArgs {
   float omb1, beta2, omb2, eps;  // omb1 = float32(1 - beta1), omb2 = float32(1 - beta2)
 };
 
+// LAMB (optim/lamb.py; You et al. 2020): ``side`` non-null selects the LAMB instantiations, which
+// need AdamArgs (else -1) and exclude LarsArgs (-1). The rule is AdamW's up to u, then
+//     r   = fma(wd, p, a1 * u)                      the update direction, weight decay inside
+//     wn  = sqrt(sum p^2),  rn = sqrt(sum r^2)      over the tensor's own elements, p BEFORE the update
+//     trust = wn / rn  if the tensor is adapted and wn > 0 and rn > 0,  else 1.0
+//     p'  = fma(-(lr * trust), r, p)                -(lr * trust): one fp32 product, once per block
+// ``side`` and ``tensors`` as LarsArgs'; ``partial`` is what ddp_lamb_norms wrote (LambNorms),
+// launched before the update on the same stream: the update forms the same r again, bit for bit
+// (optim.hip lamb_dir). A step the guard skips uses 1.0 and leaves ``trust`` as it is.
+struct LambArgs {
+  const int2* side;       // per work item: {parameter index | -1 (no ratio: item 5), first item}
+  const int4* tensors;    // per parameter: {first global chunk, chunks, adapted, -}
+  const float2* partial;  // per global chunk: {sum p^2, sum r^2}
+  float* trust;           // per parameter (written)
+};
+
+// LAMB's norms launch (optim.hip lamb_norms_kernel): one block per chunk item {arena offset,
+// count <= 8192, global chunk, -} of the adapted tensors reads p, g, m, v, stores none of m', v',
+// u, r and writes {sum p^2, sum r^2} into ``partial[global chunk]``. {a1, a2} as the update reads
+// them (AdamArgs::bias at ``sched``'s step word). ``clip.partial`` non-null: the guarded
+// instantiation takes the clip coefficient from the partials ddp_grad_sumsq wrote and forms r
+// from g * (grad_scale * c); clip.stats is not written.
+struct LambNorms {
+  const int4* items;
+  int n_items;
+  const float* p;         // the arenas: masters, gradients, first moment
+  const float* g;
+  const float* m;
+  const LrSched* sched;
+  float wd, grad_scale;
+  AdamArgs adam;          // v: read only
+  float2* partial;
+  ClipArgs clip;          // optional: clip.partial == null
+};
+
 struct UpdateLaunch {
   const int4* items;      // work items, kinds 0-5 (optim.hip), one block each
   int n_items;
@@ -319,6 +354,7 @@ struct UpdateLaunch {
   ClipArgs clip;          // optional: clip.partial == null
   EmaArgs ema;            // optional: ema.ema == null
   AdamArgs adam;          // optional: adam.v == null
+  LambArgs lamb;          // optional: lamb.side == null
 };
 
 struct AugArgs {
@@ -495,7 +531,8 @@ void ddp_conv_stamps_set(void* buf, int cap);
 #endif
 int ddp_pack_conv_weights(const ddp_amd::PackDesc* descs, int n, hipStream_t st);
 // the fused SGD + re-pack launch (UpdateLaunch above); -1: a LARS pointer or clip.stats missing,
-// or AdamW with LARS, without its bias table or without a schedule
+// or AdamW with LARS, without its bias table or without a schedule, or LAMB without AdamW, with
+// LARS or with one of its pointers missing
 int ddp_sgd_pack(const ddp_amd::UpdateLaunch* u, hipStream_t st);
 // the two per-chunk sums: int4 items {arena offset, count <= 8192, global chunk, -}, one block
 // each; ``partial`` as ClipArgs::partial (float) and LarsArgs::partial (float2)
@@ -503,6 +540,9 @@ int ddp_grad_sumsq(const void* items, int n_items, const float* g, float grad_sc
                    float* partial, hipStream_t st);
 int ddp_lars_norms(const void* items, int n_items, const float* p, const float* g,
                    float grad_scale, void* partial, hipStream_t st);
+// LAMB's per-chunk {sum p^2, sum r^2} (LambNorms); -1: a pointer, the bias table or the schedule
+// is missing
+int ddp_lamb_norms(const ddp_amd::LambNorms* n, hipStream_t st);
 // tail of a pipelined step with sharded buckets: gathered small-tensor slots -> fp32 arena,
 // re-pack of channel-padded conv operands, then release-increment ``signal`` (optim.hip)
 int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,

@@ -9,7 +9,9 @@
 // exactly (momentum * 0 + d == d), so the kernel needs no first-step flag (graph friendly).
 // With AdamW (optim/adamw.py, api.h AdamArgs) the same launch applies Adam with decoupled weight
 // decay instead: the momentum arena holds the first moment, one more arena the second, and the
-// bias corrections of the step come from a device table next to the learning rate's.
+// bias corrections of the step come from a device table next to the learning rate's. With LAMB
+// (optim/lamb.py, api.h LambArgs) a norms launch over p, g, m, v runs in front (lamb_norms_kernel)
+// and the same launch scales every adapted tensor's AdamW-style update by |w| / |update|.
 //
 // pack_conv_weights re-lays the fp32 master weights (PyTorch [K][C][R][S]) into the two bf16
 // MFMA operand layouts used by conv_igemm.hip: Wc [K][R][S][Cpad] (fwd) and Wt [C][R][S][K]
@@ -95,8 +97,8 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 // ---------------------------------------------------------------------------------------------
 // Fused SGD + weight re-pack: ONE launch updates the whole arena and writes the bf16 MFMA
 // operand copies of every conv weight from the freshly updated values (no second pass over the
-// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD, EMA, ADAM>, one block per work item
-// (int4; "SGD" below is the launch's element rule, AdamW's under ADAM):
+// fp32 weights). One kernel, sgd_pack_kernel<LARS, GUARD, EMA, ADAM, LAMB>, one block per work
+// item (int4; "SGD" below is the launch's element rule, AdamW's under ADAM, LAMB's under LAMB):
 //   {0, offset, count, -}        plain elementwise chunk;
 //   {2, rel_offset, count, desc} elementwise chunk of a conv weight stored [K][R][S][C] (the GPU
 //                                arena layout, C == Cr, or 1x1): its bf16 copy Wc has the same
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 //                                the backward (conv_igemm.hip ConvArgs::sgd); bf16(p) into the
 //                                operand copy (as item 2).
 // Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs, EmaArgs,
-// AdamArgs.
+// AdamArgs, LambArgs.
 constexpr int kTileElems = 9216;  // fp32 LDS tile (36 KB)
 
 __host__ __device__ __forceinline__ void tile_dims(int RS, int* TK, int* TC) {
@@ -178,13 +180,35 @@ struct AdamRule {
   float nla, nlw;  // -(lr * a1), -(lr * wd): one fp32 product each, once per block
   float a2, eps, omb1, beta2, omb2;
 };
-template <bool ADAM>
-using RuleOf = std::conditional_t<ADAM, AdamRule, NoAdam>;
+// LAMB = true (requires ADAM): the rule of api.h LambArgs. lamb_dir is AdamW's first five lines
+// and the update direction r with the weight decay inside; the norms kernel and the update body
+// both take r from it, every fma written out, so the two passes form the same bits.
+struct LambDir {
+  float a1, a2, wd, eps, omb1, beta2, omb2;
+};
+struct LambRule : LambDir {
+  float nlt;       // -(lr * trust): one fp32 product, once per block
+  bool skip_word;  // SgdHyper::skip, read once per block in front of the trust ratio
+};
+template <bool ADAM, bool LAMB>
+using RuleOf = std::conditional_t<LAMB, LambRule, std::conditional_t<ADAM, AdamRule, NoAdam>>;
 
-template <bool LARS, bool ADAM>
+__device__ __forceinline__ float lamb_dir(float p, float g, float& m, float& v, float gs,
+                                          const LambDir& d) {
+  const float G = g * gs;
+  m = __builtin_fmaf(d.omb1, G - m, m);
+  v = __builtin_fmaf(d.omb2 * G, G, d.beta2 * v);
+  const float den = __builtin_fmaf(sqrtf(v), d.a2, d.eps);
+  const float u = m / den;
+  return __builtin_fmaf(d.wd, p, d.a1 * u);
+}
+
+template <bool LARS, bool ADAM, bool LAMB>
 __device__ __forceinline__ float sgd1(float p, float g, float& b, float& v, const SgdHyper& h,
-                                      float trust, const RuleOf<ADAM>& r) {
-  if constexpr (ADAM) {
+                                      float trust, const RuleOf<ADAM, LAMB>& r) {
+  if constexpr (LAMB) {
+    return __builtin_fmaf(r.nlt, lamb_dir(p, g, b, v, h.grad_scale, r), p);
+  } else if constexpr (ADAM) {
     const float G = g * h.grad_scale;
     b = __builtin_fmaf(r.omb1, G - b, b);
     v = __builtin_fmaf(r.omb2 * G, G, r.beta2 * v);
@@ -237,15 +261,15 @@ __device__ __forceinline__ float* v_at(float* v, size_t i) {
 
 // One element by its arena index, every path that is not 16 bytes wide: p, buf (and v) stored,
 // +0 into g under zero_grad, the EMA; returns the new p.
-template <bool LARS, bool EMA, bool ADAM>
+template <bool LARS, bool EMA, bool ADAM, bool LAMB>
 __device__ __forceinline__ float update1(float* __restrict__ p, float* __restrict__ g,
                                          float* __restrict__ buf, float* v, size_t i,
                                          const SgdHyper& h, float trust, const EmaOf<EMA>& m,
-                                         const RuleOf<ADAM>& r) {
+                                         const RuleOf<ADAM, LAMB>& r) {
   float b = buf[i];
   float vv = 0.f;  // (unused without ADAM)
   if constexpr (ADAM) vv = v[i];
-  const float np = sgd1<LARS, ADAM>(p[i], g[i], b, vv, h, trust, r);
+  const float np = sgd1<LARS, ADAM, LAMB>(p[i], g[i], b, vv, h, trust, r);
   p[i] = np;
   buf[i] = b;
   if constexpr (ADAM) v[i] = vv;
@@ -257,10 +281,10 @@ __device__ __forceinline__ float update1(float* __restrict__ p, float* __restric
 // The update of four elements (16-byte aligned) on float4 registers: p and buf (and v: v_at of
 // the same index) stored, +0 into g under zero_grad, the EMA of the four (``e``: ema_at of the
 // same index); returns the new p.
-template <bool LARS, bool EMA, bool ADAM>
+template <bool LARS, bool EMA, bool ADAM, bool LAMB>
 __device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, float* v,
                                        const SgdHyper& h, float trust, float* e,
-                                       const EmaOf<EMA>& m, const RuleOf<ADAM>& r) {
+                                       const EmaOf<EMA>& m, const RuleOf<ADAM, LAMB>& r) {
   float4 pv = *reinterpret_cast<float4*>(p);
   const float4 gv = *reinterpret_cast<const float4*>(g);
   float4 bv = *reinterpret_cast<float4*>(buf);
@@ -268,10 +292,10 @@ __device__ __forceinline__ float4 sgd4(float* p, float* g, float* buf, float* v,
   if constexpr (ADAM) vv = *reinterpret_cast<const float4*>(v);
   float4 ev;  // (unused without EMA)
   if constexpr (EMA) ev = *reinterpret_cast<const float4*>(e);
-  pv.x = sgd1<LARS, ADAM>(pv.x, gv.x, bv.x, vv.x, h, trust, r);
-  pv.y = sgd1<LARS, ADAM>(pv.y, gv.y, bv.y, vv.y, h, trust, r);
-  pv.z = sgd1<LARS, ADAM>(pv.z, gv.z, bv.z, vv.z, h, trust, r);
-  pv.w = sgd1<LARS, ADAM>(pv.w, gv.w, bv.w, vv.w, h, trust, r);
+  pv.x = sgd1<LARS, ADAM, LAMB>(pv.x, gv.x, bv.x, vv.x, h, trust, r);
+  pv.y = sgd1<LARS, ADAM, LAMB>(pv.y, gv.y, bv.y, vv.y, h, trust, r);
+  pv.z = sgd1<LARS, ADAM, LAMB>(pv.z, gv.z, bv.z, vv.z, h, trust, r);
+  pv.w = sgd1<LARS, ADAM, LAMB>(pv.w, gv.w, bv.w, vv.w, h, trust, r);
   *reinterpret_cast<float4*>(p) = pv;
   *reinterpret_cast<float4*>(buf) = bv;
   if constexpr (ADAM) *reinterpret_cast<float4*>(v) = vv;
@@ -468,6 +492,36 @@ __device__ __forceinline__ float lars_trust_block(const LarsArgs& a, float wd, f
   return s_trust;
 }
 
+// LAMB (api.h LambArgs): the same block prologue and the same fixed order of the sums, with the
+// ratio wn / rn, rn the norm of the update direction that lamb_norms_kernel formed (from the clipped
+// gradient under the guard). (The loop is written out a second time: moved into a function of its
+// own, it changes the branch polarity hipcc picks in the four LARS instantiations, and those stay
+// instruction for instruction what they were.)
+__device__ __forceinline__ float lamb_trust_block(const LambArgs& a) {
+  __shared__ float s_trust;
+  if (threadIdx.x < 64) {
+    const int2 sd = a.side[blockIdx.x];
+    float t = 1.f;
+    if (sd.x >= 0) {
+      const int4 tn = a.tensors[sd.x];
+      if (tn.z) {
+        float sp = 0.f, sr = 0.f;
+        for (int c = threadIdx.x; c < tn.y; c += 64) {
+          const float2 v = a.partial[tn.x + c];
+          sp += v.x;
+          sr += v.y;
+        }
+        const float wn = sqrtf(wave_sum(sp)), rn = sqrtf(wave_sum(sr));
+        if (wn > 0.f && rn > 0.f) t = wn / rn;
+      }
+      if (sd.y && threadIdx.x == 0) a.trust[sd.x] = t;
+    }
+    if (threadIdx.x == 0) s_trust = t;
+  }
+  __syncthreads();
+  return s_trust;
+}
+
 // The guard's verdict of this step, the same in every block of the launch.
 struct GuardState {
   float norm, c;  // sqrt(sum (g * grad_scale)^2) over every parameter element; clip coefficient
@@ -509,18 +563,22 @@ __device__ __forceinline__ void guard_clear(const int4& it, const ConvDesc* __re
   for (int i = threadIdx.x; i < it.z; i += 256) gp[i] = 0.f;
 }
 
-template <bool LARS, bool GUARD, bool EMA, bool ADAM>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB>
 __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
                                               const ConvDesc* __restrict__ descs,
                                               float* __restrict__ p, float* __restrict__ g,
                                               float* __restrict__ buf, const SgdHyper& h,
                                               float* tile, float trust, const GuardState& gd,
                                               const EmaOf<EMA>& m, float* v,
-                                              const RuleOf<ADAM>& r) {
+                                              const RuleOf<ADAM, LAMB>& r) {
   const int4 it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
-  if (block_skip(h.skip)) return;
+  if constexpr (LAMB) {  // (the kernel read the word already: it stores no ratio either)
+    if (r.skip_word) return;
+  } else {
+    if (block_skip(h.skip)) return;
+  }
   if constexpr (GUARD) {
     if (blockIdx.x == 0 && tid == 0) {  // behind the skip word: a timed-out step records nothing
       gd.stats[0] = gd.norm;
@@ -541,11 +599,11 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t off = elem_offset(it, descs);
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
         if (i + 4 <= cnt && ((off + i) & 3) == 0) {
-          sgd4<LARS, EMA, ADAM>(p + off + i, g + off + i, buf + off + i, v_at<ADAM>(v, off + i),
+          sgd4<LARS, EMA, ADAM, LAMB>(p + off + i, g + off + i, buf + off + i, v_at<ADAM>(v, off + i),
                                 h, trust, ema_at<EMA>(m, off + i), m, r);
         } else {
           for (int e = i; e < min(cnt, i + 4); ++e)
-            update1<LARS, EMA, ADAM>(p, g, buf, v, off + e, h, trust, m, r);
+            update1<LARS, EMA, ADAM, LAMB>(p, g, buf, v, off + e, h, trust, m, r);
         }
       }
       break;
@@ -555,7 +613,7 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
         const size_t off = elem_offset(it, descs);
         float* slot = it.w >= 0 && h.slot ? h.slot + it.w : nullptr;
         for (int i = tid * 4; i < cnt; i += 256 * 4) {
-          const float4 pv = sgd4<LARS, EMA, ADAM>(p + off + i, g + off + i, buf + off + i, nullptr,
+          const float4 pv = sgd4<LARS, EMA, ADAM, LAMB>(p + off + i, g + off + i, buf + off + i, nullptr,
                                                   h, trust, ema_at<EMA>(m, off + i), m, r);
           if (h.shadow) *reinterpret_cast<uint2*>(h.shadow + off + i) = bf16x4(pv);
           if (slot) *reinterpret_cast<float4*>(slot + i) = pv;
@@ -573,7 +631,7 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const size_t base = elem_offset(it, descs);
       unsigned short* wc = descs[it.w].wc + (unsigned)it.y;
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
-        const float4 pv = sgd4<LARS, EMA, ADAM>(p + base + i, g + base + i, buf + base + i,
+        const float4 pv = sgd4<LARS, EMA, ADAM, LAMB>(p + base + i, g + base + i, buf + base + i,
                                                 v_at<ADAM>(v, base + i), h, trust,
                                                 ema_at<EMA>(m, base + i), m, r);
         *reinterpret_cast<uint2*>(wc + i) = bf16x4(pv);
@@ -592,7 +650,7 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const Tile t(d, it);
       // 1) SGD on the master for the tile's real channels, new values into the LDS tile
       t.for_each_master([&](size_t gi, int li) {
-        tile[li] = update1<LARS, EMA, ADAM>(p, g, buf, v, gi, h, trust, m, r);
+        tile[li] = update1<LARS, EMA, ADAM, LAMB>(p, g, buf, v, gi, h, trust, m, r);
       });
       __syncthreads();
       // 2) Wc[k][r][s][c] (c fastest, zero for padded channels)
@@ -618,14 +676,17 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
 }
 
 // The kernel's arguments behind the tables and arenas (their __restrict__ keeps the table reads
-// scalar): SgdHyper, then LarsArgs, ClipArgs, EmaArgs and AdamArgs only in the instantiations
-// that read them (an empty base takes no kernarg bytes; an empty struct argument would).
+// scalar): SgdHyper, then LarsArgs, ClipArgs, EmaArgs, AdamArgs and LambArgs only in the
+// instantiations that read them (an empty base takes no kernarg bytes; an empty struct argument
+// would).
 struct NoLars {};
 struct NoClip {};
-template <bool LARS, bool GUARD, bool EMA, bool ADAM>
+struct NoLamb {};
+template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB = false>
 struct UpdateArgs : SgdHyper, std::conditional_t<LARS, LarsArgs, NoLars>,
                     std::conditional_t<GUARD, ClipArgs, NoClip>, EmaOf<EMA>,
-                    std::conditional_t<ADAM, AdamArgs, NoAdam> {};
+                    std::conditional_t<ADAM, AdamArgs, NoAdam>,
+                    std::conditional_t<LAMB, LambArgs, NoLamb> {};
 static_assert(sizeof(UpdateArgs<false, false, false, false>) == 96 &&
               sizeof(UpdateArgs<false, true, false, false>) == 128 &&
               sizeof(UpdateArgs<true, false, false, false>) == 136 &&
@@ -637,8 +698,12 @@ static_assert(sizeof(UpdateArgs<false, false, false, false>) == 96 &&
               sizeof(UpdateArgs<false, false, false, true>) == 136 &&
               sizeof(UpdateArgs<false, true, false, true>) == 168 &&
               sizeof(UpdateArgs<false, false, true, true>) == 152 &&
-              sizeof(UpdateArgs<false, true, true, true>) == 184,
-              "kernarg bytes of the twelve instantiations (ADAM excludes LARS)");
+              sizeof(UpdateArgs<false, true, true, true>) == 184 &&
+              sizeof(UpdateArgs<false, false, false, true, true>) == 168 &&
+              sizeof(UpdateArgs<false, true, false, true, true>) == 200 &&
+              sizeof(UpdateArgs<false, false, true, true, true>) == 184 &&
+              sizeof(UpdateArgs<false, true, true, true, true>) == 216,
+              "kernarg bytes of the sixteen instantiations (ADAM excludes LARS, LAMB needs ADAM)");
 
 // ADAM: this step's {learning rate, a1, a2} (api.h AdamArgs), read once per block where the plain
 // instantiations read the learning rate: thread 0 loads, LDS broadcast, one barrier. The step
@@ -659,19 +724,120 @@ __device__ __forceinline__ AdamRule adam_rule_block(const AdamArgs& a, const Sgd
   return AdamRule{s_rule[0], s_rule[1], s_rule[2], a.eps, a.omb1, a.beta2, a.omb2};
 }
 
-template <bool LARS, bool GUARD, bool EMA, bool ADAM>
+// LAMB: this step's learning rate (into ``lr``) and the update direction's constants, both passes'
+// (lamb_norms_kernel, the LAMB instantiations of sgd_pack_kernel): the table reads of
+// adam_rule_block, the products left to lamb_dir and to the trust ratio.
+__device__ __forceinline__ LambDir lamb_dir_block(const AdamArgs& a, const LrSched* s, float wd,
+                                                  float* lr) {
+  __shared__ float s_tab[3];
+  if (threadIdx.x == 0) {
+    const unsigned k = __hip_atomic_load(&s->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned n = s->n;
+    const float2 bc = a.bias[k < a.n_bias ? k : a.n_bias - 1];
+    s_tab[0] = reinterpret_cast<const float*>(s + 1)[k < n ? k : n - 1];
+    s_tab[1] = bc.x;
+    s_tab[2] = bc.y;
+  }
+  __syncthreads();
+  *lr = s_tab[0];
+  return LambDir{s_tab[1], s_tab[2], wd, a.eps, a.omb1, a.beta2, a.omb2};
+}
+
+// LAMB's norms pass (api.h LambNorms): chunk_sums_kernel's shape over p, g, m, v. One block per
+// chunk item forms m', v', u and r of its elements in registers, stores none of them, and writes
+// {sum p^2, sum r^2} into the chunk's global slot. GUARD: r is not linear in the clip coefficient,
+// so the block takes it from the guard's partials first (clip_block: the update launch's own
+// fixed-order sum, the same bits) and forms r from g * (grad_scale * c). On a step the guard will
+// skip the sums may be anything: no block of the update reads them.
+template <bool GUARD>
+struct LambNormArgs : std::conditional_t<GUARD, ClipArgs, NoClip> {
+  const int4* items;  // as ChunkSumArgs::items
+  const float* p;
+  const float* g;
+  const float* m;
+  const LrSched* sched;
+  float wd, grad_scale;
+  AdamArgs adam;      // v (read only), the bias table and the rule's constants
+  float2* partial;
+};
+
+template <bool GUARD>
+__global__ __launch_bounds__(256) void lamb_norms_kernel(LambNormArgs<GUARD> a) {
+  const int4 it = a.items[blockIdx.x];
+  const size_t off = (size_t)(unsigned)it.x;
+  const int cnt = it.y, n4 = cnt >> 2;
+  const int tid = threadIdx.x;
+  float lr;  // (not needed here)
+  const LambDir d = lamb_dir_block(a.adam, a.sched, a.wd, &lr);
+  float gs = a.grad_scale;
+  if constexpr (GUARD) gs *= clip_block(a).c;
+  const float* __restrict__ p = a.p + off;
+  const float* __restrict__ g = a.g + off;
+  const float* __restrict__ m = a.m + off;
+  const float* __restrict__ v = a.adam.v + off;
+  constexpr int kIter = kNormChunk / (256 * 4);
+  float4 pv[kIter], gv[kIter], mv[kIter], vv[kIter];
+#pragma unroll
+  for (int j = 0; j < kIter; ++j) {  // every 16-byte load of the chunk in flight at once
+    const int i = tid + 256 * j;
+    if (i < n4) {
+      pv[j] = reinterpret_cast<const float4*>(p)[i];
+      gv[j] = reinterpret_cast<const float4*>(g)[i];
+      mv[j] = reinterpret_cast<const float4*>(m)[i];
+      vv[j] = reinterpret_cast<const float4*>(v)[i];
+    }
+  }
+  float sp = 0.f, sr = 0.f;  // one serial fma chain per thread: 4 * kIter (+ 1 tail) terms
+#pragma unroll
+  for (int j = 0; j < kIter; ++j) {
+    if (tid + 256 * j < n4) {  // (no zero stand-ins: with eps == 0 they would give u = 0 / 0)
+      const float* pp = &pv[j].x;
+      const float* gg = &gv[j].x;
+      float* mm = &mv[j].x;
+      float* ww = &vv[j].x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float r = lamb_dir(pp[e], gg[e], mm[e], ww[e], gs, d);
+        sp = __builtin_fmaf(pp[e], pp[e], sp);
+        sr = __builtin_fmaf(r, r, sr);
+      }
+    }
+  }
+  const int t = (n4 << 2) + tid;  // scalar tail: numel not a multiple of 4
+  if (t < cnt) {
+    float mt = m[t], vt = v[t];
+    const float r = lamb_dir(p[t], g[t], mt, vt, gs, d);
+    sp = __builtin_fmaf(p[t], p[t], sp);
+    sr = __builtin_fmaf(r, r, sr);
+  }
+  sp = wave_sum(sp);
+  sr = wave_sum(sr);
+  __shared__ float2 s_w[4];  // per wave
+  if ((tid & 63) == 0) s_w[tid >> 6] = make_float2(sp, sr);
+  __syncthreads();
+  if (tid == 0) {
+    a.partial[it.z] = make_float2(((s_w[0].x + s_w[1].x) + s_w[2].x) + s_w[3].x,
+                                  ((s_w[0].y + s_w[1].y) + s_w[2].y) + s_w[3].y);
+  }
+}
+
+template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
                                                        const ConvDesc* __restrict__ descs,
                                                        float* __restrict__ p,
                                                        float* __restrict__ g,
                                                        float* __restrict__ buf,
-                                                       UpdateArgs<LARS, GUARD, EMA, ADAM> a) {
+                                                       UpdateArgs<LARS, GUARD, EMA, ADAM, LAMB> a) {
   static_assert(!(LARS && ADAM), "AdamW has no trust ratios");
+  static_assert(ADAM || !LAMB, "LAMB is a rule on AdamW's moments");
   __shared__ float tile[kTileElems];
   SgdHyper h = a;
-  RuleOf<ADAM> rule{};
+  RuleOf<ADAM, LAMB> rule{};
   float* v = nullptr;  // (stays null and unread without ADAM)
-  if constexpr (ADAM) {
+  if constexpr (LAMB) {
+    static_cast<LambDir&>(rule) = lamb_dir_block(a, h.sched, h.wd, &h.lr);
+    v = a.v;
+  } else if constexpr (ADAM) {
     rule = adam_rule_block(a, h);
     v = a.v;
   } else {
@@ -683,8 +849,14 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
   float trust = 1.f;
   // (a skipped step leaves the stored ratios as they are)
   if constexpr (LARS) trust = GUARD && gd.skipped ? 1.f : lars_trust_block<GUARD>(a, h.wd, gd.c);
+  if constexpr (LAMB) {  // (the skip word keeps precedence: nothing is touched or recorded)
+    rule.skip_word = block_skip(h.skip);
+    const bool none = rule.skip_word || (GUARD && gd.skipped);
+    rule.nlt = -(h.lr * (none ? 1.f : lamb_trust_block(a)));
+  }
   if constexpr (GUARD) h.grad_scale *= gd.c;
-  sgd_pack_body<LARS, GUARD, EMA, ADAM>(items, descs, p, g, buf, h, tile, trust, gd, a, v, rule);
+  sgd_pack_body<LARS, GUARD, EMA, ADAM, LAMB>(items, descs, p, g, buf, h, tile, trust, gd, a, v,
+                                              rule);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
@@ -738,17 +910,28 @@ __global__ void counter_add_kernel(int* c, int delta, LrSched* sched, int sched_
   __hip_atomic_store(&sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool LARS, bool GUARD, bool EMA, bool ADAM = false>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM = false, bool LAMB = false>
 static int launch_update(const UpdateLaunch& u, hipStream_t st) {
-  UpdateArgs<LARS, GUARD, EMA, ADAM> a{};
+  UpdateArgs<LARS, GUARD, EMA, ADAM, LAMB> a{};
   static_cast<SgdHyper&>(a) = u.h;
   a.sched_advance = a.sched && a.sched_advance ? 1 : 0;
   if constexpr (LARS) static_cast<LarsArgs&>(a) = u.lars;
   if constexpr (GUARD) static_cast<ClipArgs&>(a) = u.clip;
   if constexpr (EMA) static_cast<EmaArgs&>(a) = u.ema;
   if constexpr (ADAM) static_cast<AdamArgs&>(a) = u.adam;
-  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA, ADAM>), dim3(u.n_items), dim3(256), 0, st, u.items,
-                     u.descs, u.p, u.g, u.buf, a);
+  if constexpr (LAMB) static_cast<LambArgs&>(a) = u.lamb;
+  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA, ADAM, LAMB>), dim3(u.n_items), dim3(256), 0,
+                     st, u.items, u.descs, u.p, u.g, u.buf, a);
+  return (int)hipGetLastError();
+}
+
+template <bool GUARD>
+static int launch_lamb_norms(const LambNorms& n, hipStream_t st) {
+  LambNormArgs<GUARD> a{};
+  if constexpr (GUARD) static_cast<ClipArgs&>(a) = n.clip;
+  a.items = n.items; a.p = n.p; a.g = n.g; a.m = n.m; a.sched = n.sched;
+  a.wd = n.wd; a.grad_scale = n.grad_scale; a.adam = n.adam; a.partial = n.partial;
+  hipLaunchKernelGGL(lamb_norms_kernel<GUARD>, dim3(n.n_items), dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 
@@ -800,8 +983,18 @@ extern "C" int ddp_sgd_pack(const UpdateLaunch* u, hipStream_t st) {
   const bool lars = u->lars.side, guard = u->clip.partial;
   if (guard && (!u->clip.stats || u->clip.n_chunks < 0)) return -1;
   if (lars && (!u->lars.tensors || !u->lars.partial || !u->lars.trust)) return -1;
+  const bool lamb = u->lamb.side;
+  if (lamb && (!u->adam.v || lars || !u->lamb.tensors || !u->lamb.partial || !u->lamb.trust))
+    return -1;
   if (u->adam.v) {  // AdamW: the step number comes from the schedule's step word
     if (lars || !u->adam.bias || !u->adam.n_bias || !u->h.sched) return -1;
+    if (lamb) {
+      if (u->ema.ema)
+        return (guard ? launch_update<false, true, true, true, true>
+                      : launch_update<false, false, true, true, true>)(*u, st);
+      return (guard ? launch_update<false, true, false, true, true>
+                    : launch_update<false, false, false, true, true>)(*u, st);
+    }
     if (u->ema.ema)
       return (guard ? launch_update<false, true, true, true>
                     : launch_update<false, false, true, true>)(*u, st);
@@ -823,6 +1016,14 @@ extern "C" int ddp_grad_sumsq(const void* items, int n_items, const float* g, fl
 extern "C" int ddp_lars_norms(const void* items, int n_items, const float* p, const float* g,
                               float grad_scale, void* partial, hipStream_t st) {
   return launch_chunk_sums<true>(items, n_items, p, g, grad_scale, (float2*)partial, st);
+}
+
+extern "C" int ddp_lamb_norms(const LambNorms* n, hipStream_t st) {
+  if (n->n_items <= 0) return 0;
+  const bool guard = n->clip.partial;
+  if (!n->items || !n->p || !n->g || !n->m || !n->adam.v || !n->partial) return -1;
+  if (!n->adam.bias || !n->adam.n_bias || !n->sched || (guard && n->clip.n_chunks < 0)) return -1;
+  return (guard ? launch_lamb_norms<true> : launch_lamb_norms<false>)(*n, st);
 }
 
 extern "C" int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,

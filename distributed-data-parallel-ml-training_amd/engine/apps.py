@@ -63,7 +63,7 @@ def main(part, argv=None):
                                         captured=captured)
     # --lr / --lr-schedule ... (opt-in; default: the reference's constant 0.1, nothing attached)
     lr, schedule = lr_schedule_from_args(args, len(train_loader))
-    optimizer = optimizer_from_args(args, model.parameters(), lr)  # --optimizer sgd | lars | adamw
+    optimizer = optimizer_from_args(args, model.parameters(), lr)  # --optimizer sgd | lars | adamw | lamb
     if schedule is not None:
         optimizer.set_schedule(schedule)
     # --ema-decay (opt-in): the average starts as a copy of the weights, so it is switched on

@@ -40,14 +40,13 @@ new master; nothing else changes (LARS already keeps every update in the step's 
 import torch
 
 from .sgd import FusedSGD
+from .trust import TrustTables
 
 _SHARDED = ("LARS needs every tensor's whole gradient for its norm: the sharded updates split "
             "tensors across ranks; use the replicated update, update=\"allreduce\"")
 
 
-class LARS(FusedSGD):
-    needs_whole_tensors = True
-
+class LARS(TrustTables, FusedSGD):
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, grad_scale=1.0, trust_coefficient=0.001, eps=1e-8,
                  exclude_1d=True, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False):
@@ -63,66 +62,7 @@ class LARS(FusedSGD):
                  "exclude_1d": bool(exclude_1d)}
         self.defaults.update(hyper)
         self.param_groups[0].update(hyper)
-        self._trust_cpu = None
-        if self._fused:
-            a, dev = self.arena, self.arena.data.device
-            # allocated once: captured launches keep these addresses
-            self._lars_partial = torch.zeros(max(self._n_chunks, 1), 2, dtype=torch.float32,
-                                             device=dev)
-            self._lars_trust = torch.ones(len(a.params), dtype=torch.float32, device=dev)
-            self._lars_tensors = torch.zeros(len(a.params), 4, dtype=torch.int32, device=dev)
-            self._adapted_for = None
-            self._norm_tables = {}
-            self._side_tables, self._side_for = {}, None
-
-    # ------------------------------------------------------------------------------- tables
-    def _adapted(self):
-        ex = bool(self.param_groups[0]["exclude_1d"])
-        return [p.dim() > 1 or not ex for p in self.param_groups[0]["params"]]
-
-    def _tensor_table(self):
-        """Per parameter {first global chunk, chunks, adapted, -}: written in place when
-        ``exclude_1d`` changes (not inside a capture: change it before capturing)."""
-        ex = bool(self.param_groups[0]["exclude_1d"])
-        if self._adapted_for != ex:
-            ad, a = self._adapted(), self.arena
-            rows = [[self._chunk0[i], -(-a.numels[i] // self.CHUNK), int(ad[i]), 0]
-                    for i in range(len(a.params))]
-            self._lars_tensors.copy_(torch.tensor(rows, dtype=torch.int32))
-            self._adapted_for = ex
-            self._norm_tables = {}
-        return self._lars_tensors
-
-    def _norm_table(self, rng):
-        """Work items of the norms launch over parameters [i0, i1): FusedSGD._chunk_table over
-        the adapted tensors; cached per range."""
-        if rng not in self._norm_tables:
-            self._norm_tables[rng] = self._chunk_table(rng, self._adapted())
-        return self._norm_tables[rng]
-
-    def _side_table(self, key):
-        """Side table parallel to the work-item table ``key`` of FusedSGD._work_table: per item
-        {parameter index | -1, 1 on the tensor's first item (that block stores the ratio)}."""
-        if self._side_for is not self._tables:  # the work tables were rebuilt
-            self._side_tables, self._side_for = {}, self._tables
-        t = self._side_tables.get(key)
-        if t is None:
-            seen, rows = set(), []
-            for i in self._tables[key][2]:
-                rows.append([i, int(i >= 0 and i not in seen)])
-                seen.add(i)
-            t = torch.tensor(rows, dtype=torch.int32, device=self.arena.data.device)
-            self._side_tables[key] = t
-        return t
-
-    def trust_ratios(self):
-        """Per-parameter trust ratios of the last update of each tensor (1.0: not adapted, or a
-        zero norm). GPU: the device array the update kernel writes, as is (no sync)."""
-        if self._fused:
-            return self._lars_trust
-        if self._trust_cpu is None:
-            self._trust_cpu = torch.ones(len(self.param_groups[0]["params"]))
-        return self._trust_cpu
+        self._alloc_trust_tables()
 
     # ------------------------------------------------------------------------------ refusals
     def register_in_backward(self):
@@ -197,21 +137,18 @@ class LARS(FusedSGD):
         a = self.arena
         rng = tuple(params) if params is not None else (0, len(a.params))
         items, n_items, descs = self._work_table(params)
-        side = self._side_table((rng, frozenset(), frozenset()))
-        tensors = self._tensor_table()
+        tables = self._trust_kw("lars", rng)
         nitems, n_norm = self._norm_table(rng)
         gs = float(self._grad_scale_factor)
         if self.guarded and not norm_done:
             self.grad_sumsq(params, stream)
         if n_norm:
             native().lars_norms(nitems.data_ptr(), n_norm, a.data.data_ptr(), a.grad.data_ptr(),
-                                gs, self._lars_partial.data_ptr(), s)
+                                gs, self._trust_partial.data_ptr(), s)
         self._update_launch(items, n_items, s, descs=descs, zero_grad=zero_grad, counter=counter,
                             skip=skip, signal=signal, lr_advance=lr_advance,
-                            lars_side=side.data_ptr(), lars_tensors=tensors.data_ptr(),
-                            lars_partial=self._lars_partial.data_ptr(),
-                            lars_trust=self._lars_trust.data_ptr(),
-                            lars_eta=float(g["trust_coefficient"]), lars_eps=float(g["eps"]))
+                            lars_eta=float(g["trust_coefficient"]), lars_eps=float(g["eps"]),
+                            **tables)
         return None
 
     def load_state_dict(self, sd):

@@ -72,18 +72,21 @@ def build_parser(description=None, distributed=True):
     g.add_argument('--min-lr', type=float, default=0.0, help='end value of cosine / linear')
     g.add_argument('--lr-ref-batch', type=int, default=None,
                    help='linear scaling rule: lr *= global batch / this batch')
-    g.add_argument('--optimizer', default='sgd', choices=['sgd', 'lars', 'adamw'],
+    g.add_argument('--optimizer', default='sgd', choices=['sgd', 'lars', 'adamw', 'lamb'],
                    help='sgd (reference) | lars: every weight tensor\'s update scaled by its trust '
                         'ratio eta |w| / (|g| + wd |w| + eps), for the learning rates that the '
                         'linear scaling rule gives a large global batch (works inside --graph) | '
                         'adamw: Adam with decoupled weight decay (torch.optim.AdamW) inside the '
-                        'update launch (works inside --graph; pass an Adam-sized --lr, 0.001)')
+                        'update launch (works inside --graph; pass an Adam-sized --lr, 0.001) | '
+                        'lamb: the AdamW update with every weight tensor\'s step scaled by its '
+                        'trust ratio |w| / |update|, for Adam at a large global batch (one more '
+                        'launch per update; works inside --graph)')
     g.add_argument('--adam-beta1', type=_adam_beta, default=0.9)
     g.add_argument('--adam-beta2', type=_adam_beta, default=0.999)
     g.add_argument('--adam-eps', type=_non_negative('--adam-eps'), default=1e-8)
     g.add_argument('--weight-decay', type=_non_negative('--weight-decay'), default=None,
                    help="weight decay; default: the optimizer's own, 1e-4 for sgd and lars "
-                        "(reference), 1e-2 for adamw")
+                        "(reference), 1e-2 for adamw and lamb")
     g.add_argument('--lars-eta', type=float, default=0.001, help='LARS trust coefficient')
     g.add_argument('--lars-eps', type=float, default=1e-8)
     g.add_argument('--clip-grad-norm', type=float, default=None,
@@ -160,21 +163,23 @@ def _accum_steps(v):
 def optimizer_from_args(args, params, lr):
     """The run's optimizer: the reference's SGD(lr, 0.9, 1e-4), or LARS over the same
     hyper-parameters with --optimizer lars (biases and BatchNorm vectors are not adapted), or
-    AdamW(lr, (--adam-beta1, --adam-beta2), --adam-eps, 1e-2) with --optimizer adamw;
+    AdamW(lr, (--adam-beta1, --adam-beta2), --adam-eps, 1e-2) with --optimizer adamw, or LAMB over
+    AdamW's hyper-parameters with --optimizer lamb (biases and BatchNorm vectors are not adapted);
     --weight-decay replaces the optimizer's default decay; --clip-grad-norm /
     --skip-nonfinite-grads switch the gradient guard of any of them on."""
-    from ..optim import FusedSGD, LARS, AdamW
+    from ..optim import FusedSGD, LAMB, LARS, AdamW
     guard = {}
     if getattr(args, "clip_grad_norm", None) is not None or \
             getattr(args, "skip_nonfinite_grads", False):
         guard = {"max_grad_norm": getattr(args, "clip_grad_norm", None),
                  "skip_nonfinite": bool(getattr(args, "skip_nonfinite_grads", False))}
     wd = getattr(args, "weight_decay", None)
-    if getattr(args, "optimizer", "sgd") == "adamw":
-        return AdamW(params, lr=lr, betas=(getattr(args, "adam_beta1", 0.9),
-                                           getattr(args, "adam_beta2", 0.999)),
-                     eps=getattr(args, "adam_eps", 1e-8),
-                     weight_decay=0.01 if wd is None else wd, **guard)
+    if getattr(args, "optimizer", "sgd") in ("adamw", "lamb"):
+        cls = LAMB if args.optimizer == "lamb" else AdamW
+        return cls(params, lr=lr, betas=(getattr(args, "adam_beta1", 0.9),
+                                         getattr(args, "adam_beta2", 0.999)),
+                   eps=getattr(args, "adam_eps", 1e-8),
+                   weight_decay=0.01 if wd is None else wd, **guard)
     wd = 0.0001 if wd is None else wd
     if getattr(args, "optimizer", "sgd") == "lars":
         return LARS(params, lr=lr, momentum=0.9, weight_decay=wd,
