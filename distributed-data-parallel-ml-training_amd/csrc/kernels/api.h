@@ -325,7 +325,9 @@ struct LambArgs {
 
 // LAMB's norms launch (optim.hip lamb_norms_kernel): one block per chunk item {arena offset,
 // count <= 8192, global chunk, -} of the adapted tensors reads p, g, m, v, stores none of m', v',
-// u, r and writes {sum p^2, sum r^2} into ``partial[global chunk]``. {a1, a2} as the update reads
+// u, r and writes {sum p^2, sum r^2} into ``partial[global chunk]``. Bit 0 of an item's fourth
+// field: the chunk's tensor is not weight-decayed, r is formed with wd = 0 (the update launch
+// does the same for the items that carry bit 8 of their kind word). {a1, a2} as the update reads
 // them (AdamArgs::bias at ``sched``'s step word). ``clip.partial`` non-null: the guarded
 // instantiation takes the clip coefficient from the partials ddp_grad_sumsq wrote and forms r
 // from g * (grad_scale * c); clip.stats is not written.
@@ -343,7 +345,8 @@ struct LambNorms {
 };
 
 struct UpdateLaunch {
-  const int4* items;      // work items, kinds 0-5 (optim.hip), one block each
+  const int4* items;      // work items, kinds 0-5 (optim.hip), one block each; kind word | 0x100
+                          // on an updating item: SgdHyper::wd is 0 for that block
   int n_items;
   const ConvDesc* descs;
   float* p;               // the three arenas: masters, gradients, momentum

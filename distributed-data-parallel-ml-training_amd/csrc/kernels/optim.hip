@@ -117,9 +117,17 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 //   {5, rel_offset, count, desc} operand re-pack only — the fp32 master was already updated by
 //                                the backward (conv_igemm.hip ConvArgs::sgd); bf16(p) into the
 //                                operand copy (as item 2).
+// The kind is the low byte of the first word. Bit 8 (kItemNoDecay) on an updating item (kinds
+// 0-3): its tensor is not weight-decayed (optim/sgd.py ``no_decay``) — the block runs the same
+// rule with wd = 0, taken once per block in front of the prologues that use it. Never set on
+// kinds 4 and 5.
 // Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs, EmaArgs,
 // AdamArgs, LambArgs.
 constexpr int kTileElems = 9216;  // fp32 LDS tile (36 KB)
+constexpr int kItemKindMask = 0xff;
+constexpr int kItemNoDecay = 0x100;
+
+__device__ __forceinline__ int item_kind(const int4& it) { return it.x & kItemKindMask; }
 
 __host__ __device__ __forceinline__ void tile_dims(int RS, int* TK, int* TC) {
   if (RS == 1) { *TK = 64; *TC = 64; }
@@ -318,7 +326,8 @@ __device__ __forceinline__ uint2 bf16x4(const float4& v) {
 // Arena offset of an elementwise item's first element (kinds 0, 3, 4: absolute; 2, 5: relative
 // to their conv master).
 __device__ __forceinline__ size_t elem_offset(const int4& it, const ConvDesc* __restrict__ descs) {
-  return (it.x == 2 || it.x == 5 ? (size_t)descs[it.w].p_offset : 0) + (unsigned)it.y;
+  const int kind = item_kind(it);
+  return (kind == 2 || kind == 5 ? (size_t)descs[it.w].p_offset : 0) + (unsigned)it.y;
 }
 
 // A tile item {1, desc, k0, c0}: TK x TC x (R*S) weights from (k0, c0), cut at the tensor's edges.
@@ -555,7 +564,7 @@ __device__ __forceinline__ GuardState clip_block(const ClipArgs& a) {
 // A skipped step's share of a work item of kind 0-3: its gradient range, cleared.
 __device__ __forceinline__ void guard_clear(const int4& it, const ConvDesc* __restrict__ descs,
                                             float* __restrict__ g) {
-  if (it.x == 1) {
+  if (item_kind(it) == 1) {
     Tile(descs[it.y], it).for_each_master([&](size_t gi, int) { g[gi] = 0.f; });
     return;
   }
@@ -572,6 +581,7 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
                                               const EmaOf<EMA>& m, float* v,
                                               const RuleOf<ADAM, LAMB>& r) {
   const int4 it = items[blockIdx.x];
+  const int kind = item_kind(it);
   const int tid = threadIdx.x;
   if (h.counter && blockIdx.x == 0 && tid == 0) atomicAdd(h.counter, h.delta);
   if constexpr (LAMB) {  // (the kernel read the word already: it stores no ratio either)
@@ -588,13 +598,13 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
         *n = *n + 1u;
       }
     }
-    if (gd.skipped && it.x != 4 && it.x != 5) {
+    if (gd.skipped && kind != 4 && kind != 5) {
       if (h.zero_grad) guard_clear(it, descs, g);
       return;
     }
   }
   const int cnt = it.z;  // (elementwise items)
-  switch (it.x) {
+  switch (kind) {
     case 0: {
       const size_t off = elem_offset(it, descs);
       for (int i = tid * 4; i < cnt; i += 256 * 4) {
@@ -751,7 +761,7 @@ __device__ __forceinline__ LambDir lamb_dir_block(const AdamArgs& a, const LrSch
 // skip the sums may be anything: no block of the update reads them.
 template <bool GUARD>
 struct LambNormArgs : std::conditional_t<GUARD, ClipArgs, NoClip> {
-  const int4* items;  // as ChunkSumArgs::items
+  const int4* items;  // as ChunkSumArgs::items; bit 0 of the fourth field: wd = 0 for this chunk
   const float* p;
   const float* g;
   const float* m;
@@ -768,7 +778,7 @@ __global__ __launch_bounds__(256) void lamb_norms_kernel(LambNormArgs<GUARD> a) 
   const int cnt = it.y, n4 = cnt >> 2;
   const int tid = threadIdx.x;
   float lr;  // (not needed here)
-  const LambDir d = lamb_dir_block(a.adam, a.sched, a.wd, &lr);
+  const LambDir d = lamb_dir_block(a.adam, a.sched, (it.w & 1) ? 0.f : a.wd, &lr);
   float gs = a.grad_scale;
   if constexpr (GUARD) gs *= clip_block(a).c;
   const float* __restrict__ p = a.p + off;
@@ -832,6 +842,8 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
   static_assert(ADAM || !LAMB, "LAMB is a rule on AdamW's moments");
   __shared__ float tile[kTileElems];
   SgdHyper h = a;
+  // (a scalar load and a block-uniform select: the item table is const __restrict__)
+  if (items[blockIdx.x].x & kItemNoDecay) h.wd = 0.f;
   RuleOf<ADAM, LAMB> rule{};
   float* v = nullptr;  // (stays null and unread without ADAM)
   if constexpr (LAMB) {

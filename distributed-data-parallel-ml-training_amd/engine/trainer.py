@@ -82,7 +82,9 @@ def _optimizer_field(optimizer):
     """Extra metrics field of one iteration: the optimizer's name where it is not the reference's
     SGD family (optim/adamw.py ``metrics_name``; records of sgd and lars runs stay as they were)."""
     name = getattr(optimizer, "metrics_name", None)
-    return {} if name is None else {"optimizer": name}
+    mask = getattr(optimizer, "no_decay_name", None)  # --no-decay-1d: "1d"
+    return {**({} if name is None else {"optimizer": name}),
+            **({} if mask is None else {"no_decay": mask})}
 
 
 def micro_batch_ctx(model, first, last):

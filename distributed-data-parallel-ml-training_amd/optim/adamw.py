@@ -37,6 +37,12 @@ the backward, no ``step_elements``, no sharded update; ``update="allreduce"`` is
 LARS and the EMA. It composes with schedules, the gradient guard, accumulation, the EMA, soft
 targets and every gradient-sync strategy.
 
+``no_decay`` (FusedSGD's per-tensor mask, ``"1d"`` or an iterable of parameters): a masked
+tensor takes the rule with ``wd = 0``; ``-(lr * 0) = -0`` and ``fma(-0, p, p) = p``, so it is
+``torch.optim.AdamW`` with a ``weight_decay=0`` group, bit for bit in ``p``. The update launch
+takes the decision per work item (bit 8 of the kind word), once per block, in front of the
+``-(lr * wd)`` product. Per-group decay VALUES and learning rates are not covered.
+
 ``state_dict`` uses torch.optim.AdamW's per-parameter layout ``{"step", "exp_avg",
 "exp_avg_sq"}`` with ``step`` = ``lr_step``; a state dict written by torch.optim.AdamW for the
 same parameters loads.
@@ -82,7 +88,8 @@ class AdamW(FusedSGD):
     metrics_name = "adamw"  # the ``optimizer`` field of --metrics records
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 grad_scale=1.0, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False):
+                 grad_scale=1.0, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False,
+                 no_decay=None):
         self._check_hyper(betas, eps)
         if not float(lr) >= 0.0:
             raise ValueError("lr must be >= 0")
@@ -91,7 +98,7 @@ class AdamW(FusedSGD):
         table = bias_table(*betas)  # (refuses an unreasonable beta before anything is allocated)
         super().__init__(params, lr=lr, momentum=0.0, weight_decay=weight_decay,
                          grad_scale=grad_scale, max_grad_norm=max_grad_norm, clip_eps=clip_eps,
-                         skip_nonfinite=skip_nonfinite)
+                         skip_nonfinite=skip_nonfinite, no_decay=no_decay)
         if len(self.param_groups) != 1:
             raise ValueError("AdamW supports a single param group")
         self._bias_dev = None
@@ -174,7 +181,7 @@ class AdamW(FusedSGD):
         gs = f(self._grad_scale_factor)
         if c is not None:
             gs = gs * c
-        nla, nlw = float(-(lr * f(a1))), float(-(lr * f(g["weight_decay"])))
+        nla = float(-(lr * f(a1)))
         plist = g["params"]
         for i in range(*(params if params is not None else (0, len(plist)))):
             p = plist[i]
@@ -191,6 +198,7 @@ class AdamW(FusedSGD):
             v.copy_(fma32(omb2 * G, G, beta2 * v))
             den = fma32(a2, v.sqrt(), torch.full_like(v, _f32(g["eps"])))
             u = m / den
+            nlw = float(-(lr * f(self._wd_of(i))))  # (-0 under the no-decay mask: p stays)
             p.copy_(fma32(nla, u, fma32(nlw, p.float(), p.float())))
 
     @torch.no_grad()

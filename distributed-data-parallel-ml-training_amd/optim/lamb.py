@@ -18,10 +18,13 @@ under the gradient guard), ``{a1, a2}`` = AdamW's bias-table entry of step ``t =
     p'  = fma(-(lr * trust), r, p)                  -(lr * trust): one fp32 product
 
 A tensor is adapted when ``p.dim() > 1 or not exclude_1d`` (LARS's convention: biases and
-BatchNorm vectors get 1.0); weight decay stays on for every tensor. LAMB has one rule for every
+BatchNorm vectors get 1.0); weight decay stays on for every tensor unless the ``no_decay`` mask
+of FusedSGD takes it off (``"1d"`` or an iterable of parameters: ``r = fma(0, p, a1 u)`` for a
+masked tensor, in both passes — bit 0 of the fourth field of its norms items and bit 8 of the
+kind word of its update items select ``wd = 0`` for the block). LAMB has one rule for every
 tensor, so a tensor with trust 1.0 is NOT bitwise AdamW: ``r`` folds the decay into the
 direction, AdamW applies it to p first. There is no trust coefficient, no clamp of ``wn`` and no
-per-group weight decay.
+per-group decay value or learning rate.
 
 GPU: the ratio needs the norm of the update direction of a whole tensor before any element of it
 moves, so an update takes two launches, both captured with the step. ``lamb_norms_kernel`` runs
@@ -55,10 +58,10 @@ class LAMB(TrustTables, AdamW):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  grad_scale=1.0, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False,
-                 exclude_1d=True):
+                 exclude_1d=True, no_decay=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                          grad_scale=grad_scale, max_grad_norm=max_grad_norm, clip_eps=clip_eps,
-                         skip_nonfinite=skip_nonfinite)
+                         skip_nonfinite=skip_nonfinite, no_decay=no_decay)
         self.defaults["exclude_1d"] = bool(exclude_1d)
         self.param_groups[0]["exclude_1d"] = bool(exclude_1d)
         self._alloc_trust_tables()
@@ -75,7 +78,6 @@ class LAMB(TrustTables, AdamW):
         a1, a2 = self.bias_at(self._lr_step)
         b1, b2 = g["betas"]
         omb1, beta2, omb2 = _f32(1.0 - b1), f(b2), f(1.0 - b2)
-        wd = _f32(g["weight_decay"])
         gs = f(self._grad_scale_factor)
         if c is not None:
             gs = gs * c
@@ -95,7 +97,7 @@ class LAMB(TrustTables, AdamW):
             v.copy_(fma32(omb2 * G, G, beta2 * v))
             den = fma32(a2, v.sqrt(), torch.full_like(v, _f32(g["eps"])))
             u = m / den
-            r = fma32(wd, p.float(), f(a1) * u)
+            r = fma32(_f32(self._wd_of(i)), p.float(), f(a1) * u)
             t = torch.ones((), dtype=torch.float32)
             if adapted[i]:
                 wn = p.double().pow(2).sum().float().sqrt()

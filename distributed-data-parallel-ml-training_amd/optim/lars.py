@@ -12,7 +12,9 @@ is scaled to the size of the tensor itself. All arithmetic is fp32; ``gs`` = ``g
     p   = fma(-lr, d, p)
 
 A tensor whose ratio is 1.0 takes the plain SGD update bit for bit; weight decay stays on for
-every tensor. Conv masters are stored [K][R][S][C] on the GPU: a norm does not depend on the
+every tensor unless the ``no_decay`` mask of FusedSGD takes it off (``"1d"`` or an iterable of
+parameters): a masked tensor runs with ``wd = 0`` in the update and, when it is adapted
+(``exclude_1d=False``), in its ratio, ``eta * wn / (gn + eps)``. Conv masters are stored [K][R][S][C] on the GPU: a norm does not depend on the
 element order.
 
 GPU: two launches per update launch of FusedSGD, both captured with the step
@@ -49,13 +51,14 @@ _SHARDED = ("LARS needs every tensor's whole gradient for its norm: the sharded 
 class LARS(TrustTables, FusedSGD):
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, grad_scale=1.0, trust_coefficient=0.001, eps=1e-8,
-                 exclude_1d=True, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False):
+                 exclude_1d=True, max_grad_norm=None, clip_eps=1e-6, skip_nonfinite=False,
+                 no_decay=None):
         if dampening != 0.0:
             raise ValueError("LARS supports dampening=0 only")
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening,
                          weight_decay=weight_decay, nesterov=nesterov, grad_scale=grad_scale,
                          max_grad_norm=max_grad_norm, clip_eps=clip_eps,
-                         skip_nonfinite=skip_nonfinite)
+                         skip_nonfinite=skip_nonfinite, no_decay=no_decay)
         if len(self.param_groups) != 1:
             raise ValueError("LARS supports a single param group")
         hyper = {"trust_coefficient": float(trust_coefficient), "eps": float(eps),
@@ -78,7 +81,7 @@ class LARS(TrustTables, FusedSGD):
         """``c``: the guard's clip coefficient (fp32 tensor) or None."""
         g = self.param_groups[0]
         lr = self._cpu_lr()
-        m, wd, nesterov = float(g["momentum"]), float(g["weight_decay"]), bool(g["nesterov"])
+        m, nesterov = float(g["momentum"]), bool(g["nesterov"])
         eta, eps = float(g["trust_coefficient"]), float(g["eps"])
         gs = float(self._grad_scale_factor)
         plist, adapted, trust = g["params"], self._adapted(), self.trust_ratios()
@@ -86,6 +89,7 @@ class LARS(TrustTables, FusedSGD):
             p = plist[i]
             if p.grad is None:
                 continue
+            wd = self._wd_of(i)
             gr = p.grad * gs
             if c is not None:  # clip first: the update runs with gs * c ...
                 gr = p.grad * (torch.tensor(gs, dtype=torch.float32) * c)

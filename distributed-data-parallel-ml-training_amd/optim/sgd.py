@@ -52,6 +52,20 @@ a step the guard skipped) leaves it alone. Every update has to run in that launc
 pointer in every conv kernel's arguments — and no sharded update. ``swap_ema`` exchanges
 masters and average in place (addresses stay: captured graphs stay valid) for evaluation and
 checkpoints. On the CPU the same formula runs after each step that was not skipped.
+
+No weight decay on chosen tensors (``no_decay``; opt-in): ``"1d"`` masks every parameter with
+``p.dim() <= 1`` (biases, BatchNorm gamma / beta: the two param groups ``{weights, wd}``,
+``{1-D tensors, 0}`` of the large-batch recipes), an iterable of parameters masks exactly those.
+A masked tensor takes the same rule with ``wd = 0`` — ``d = fma(0, p, g gs)`` here, which equals
+torch.optim.SGD's skipped add but for a ``-0`` gradient, which becomes ``+0`` — and nothing else
+about its update changes. It is a mask, not a per-tensor decay value or learning rate. A
+captured launch bakes the one ``wd`` argument in, so the decision is taken per work item: bit 8
+(``NO_DECAY``) of an updating item's kind word (csrc/kernels/optim.hip), OR-ed in by
+``_work_table`` (and by ``_elem_table`` / the sharded update's items, cut where the mask
+changes), selects ``wd = 0`` for that block. No kernel argument, no launch and no table row is
+added, and with the mask off every table is byte for byte what it was. ``set_no_decay`` before
+a capture and before a sharded update object is built; the mask travels in
+``param_groups[0]["no_decay"]`` (sorted parameter indices) only when it was set.
 """
 import contextlib
 import itertools
@@ -114,10 +128,11 @@ class FusedSGD(torch.optim.SGD):
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, grad_scale=1.0, max_grad_norm=None, clip_eps=1e-6,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, no_decay=None):
         params = list(params)
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening,
                          weight_decay=weight_decay, nesterov=nesterov)
+        self._no_decay = frozenset()  # masked parameter indices (arena order)
         self._grad_scale_factor = grad_scale
         self._fused = bool(params) and params[0].is_cuda
         if self._fused:
@@ -145,6 +160,8 @@ class FusedSGD(torch.optim.SGD):
         self._set_guard(max_grad_norm, clip_eps, skip_nonfinite)
         self._ema = None        # the EMA arena (set_ema allocates it once)
         self._ema_decay = None  # None: off
+        if no_decay is not None:
+            self.set_no_decay(no_decay)
 
     @property
     def grad_scale_factor(self):
@@ -158,6 +175,90 @@ class FusedSGD(torch.optim.SGD):
     @grad_scale_factor.setter
     def grad_scale_factor(self, v):
         self._grad_scale_factor = float(v)
+
+    # ------------------------------------------------------------------------- no-decay mask
+    NO_DECAY = 0x100  # bit 8 of an updating work item's kind word (optim.hip kItemNoDecay)
+
+    def set_no_decay(self, spec):
+        """Choose the tensors that are not weight-decayed: ``None`` (none), ``"1d"`` (every
+        parameter with ``p.dim() <= 1``), an iterable of this optimizer's parameters (matched by
+        identity), or — what a state dict carries — a list of parameter indices. The mask is
+        baked into the work-item tables: call it before a capture and before a sharded update
+        object is built; every cached work, side, norm and element table is dropped.
+        ``param_groups[0]["no_decay"]`` (sorted indices) exists only while a mask is set."""
+        if len(self.param_groups) != 1:
+            raise ValueError("the no-decay mask supports a single param group")
+        g = self.param_groups[0]
+        params = g["params"]
+        if spec is None:
+            idx = None
+        elif isinstance(spec, str):
+            if spec != "1d":
+                raise ValueError(f"no_decay = {spec!r}: None, \"1d\" or an iterable of parameters")
+            idx = [i for i, p in enumerate(params) if p.dim() <= 1]
+        else:
+            where = {id(p): i for i, p in enumerate(params)}
+            idx = []
+            for t in spec:
+                if torch.is_tensor(t):
+                    if id(t) not in where:
+                        raise ValueError("no_decay: a tensor that is not a parameter of this "
+                                         "optimizer")
+                    idx.append(where[id(t)])
+                elif isinstance(t, int) and not isinstance(t, bool) and 0 <= t < len(params):
+                    idx.append(t)
+                else:
+                    raise ValueError(f"no_decay: {t!r} is neither a parameter of this optimizer "
+                                     "nor a parameter index")
+        self._no_decay = frozenset(idx or ())
+        if idx is None:
+            g.pop("no_decay", None)
+            self.defaults.pop("no_decay", None)
+        else:
+            g["no_decay"] = sorted(self._no_decay)
+            self.defaults["no_decay"] = []  # (a group added later masks nothing)
+        # every table that carries the flag
+        self._table_key = None
+        self._elem_tables = {}
+        for name in ("_sumsq_tables", "_norm_tables"):
+            if hasattr(self, name):
+                setattr(self, name, {})
+
+    @property
+    def no_decay_mask(self):
+        """One bool per parameter in arena order: True where the tensor is not decayed."""
+        return [i in self._no_decay for i in range(len(self.param_groups[0]["params"]))]
+
+    @property
+    def no_decay_name(self):
+        """The mask as --metrics records name it: None (off), "1d" (exactly the parameters with
+        ``p.dim() <= 1``), else "custom"."""
+        if not self._no_decay:
+            return None
+        one_d = {i for i, p in enumerate(self.param_groups[0]["params"]) if p.dim() <= 1}
+        return "1d" if self._no_decay == one_d else "custom"
+
+    def _wd_of(self, i):
+        """Parameter i's weight decay: the group's, or 0.0 under the mask."""
+        return 0.0 if i in self._no_decay else float(self.param_groups[0]["weight_decay"])
+
+    def _decay_runs(self, lo, hi):
+        """Arena elements [lo, hi) cut where the mask changes: (start, end, masked) runs. A
+        tensor's alignment padding goes with the tensor before it (parallel/zero.py _tensors)."""
+        a = self.arena
+        if not self._no_decay:
+            return [(lo, hi, False)]
+        ends = list(a.offsets[1:]) + [a.total]
+        runs = []
+        for i, (t0, t1) in enumerate(zip(a.offsets, ends)):
+            s, e, nd = max(lo, t0), min(hi, t1), i in self._no_decay
+            if s >= e:
+                continue
+            if runs and runs[-1][2] == nd and runs[-1][1] == s:
+                runs[-1] = (runs[-1][0], e, nd)
+            else:
+                runs.append((s, e, nd))
+        return runs
 
     # ------------------------------------------------------------------------ gradient guard
     CHUNK = 8192  # elements per elementwise item and per chunk-sum block (optim.hip kNormChunk)
@@ -221,9 +322,11 @@ class FusedSGD(torch.optim.SGD):
     def _chunk_table(self, rng, keep=None):
         """Work items of a chunk-sum launch (the guard's sum of squares, LARS' norms) over
         parameters [i0, i1), those with ``keep[i]`` if given: one per chunk, {arena offset,
-        count, global chunk number, -}. Returns (device table or None, rows)."""
+        count, global chunk number, 1 under the no-decay mask else 0}. The fourth field is read
+        by LAMB's norms launch only. Returns (device table or None, rows)."""
         a = self.arena
-        rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c, 0]
+        rows = [[a.offsets[i] + s0, min(self.CHUNK, a.numels[i] - s0), self._chunk0[i] + c,
+                 int(i in self._no_decay)]
                 for i in range(*rng) if keep is None or keep[i]
                 for c, s0 in enumerate(range(0, a.numels[i], self.CHUNK))]
         return (torch.tensor(rows, dtype=torch.int32, device=a.data.device) if rows else None,
@@ -604,7 +707,7 @@ class FusedSGD(torch.optim.SGD):
                 continue
             dw = base_g + 4 * a.offsets[i]
             nat.sgd_fuse_register(dw, pp, base_b + 4 * a.offsets[i], wc, float(g["lr"]),
-                                  float(g["momentum"]), float(g["weight_decay"]),
+                                  float(g["momentum"]), self._wd_of(i),
                                   float(self._grad_scale_factor), int(bool(g["nesterov"])),
                                   **sched)
             self._bwd_index[dw] = i
@@ -636,7 +739,7 @@ class FusedSGD(torch.optim.SGD):
         ``exclude``) = those whose bf16 operand copy is still to be re-packed here (item 5)."""
         from ..ops.common import native
         a = self.arena
-        key = tuple(self._packs())
+        key = (tuple(self._packs()), self._no_decay) if self._no_decay else tuple(self._packs())
         if getattr(self, "_table_key", None) != key:
             self._tables = {}
             self._table_key = key
@@ -671,6 +774,9 @@ class FusedSGD(torch.optim.SGD):
                 o, n = a.offsets[i], a.numels[i]
                 for s in range(0, n, self.CHUNK):
                     per_param[i].append([0, o + s, min(self.CHUNK, n - s), 0])
+            for i in self._no_decay:  # the block of a masked tensor's item runs with wd = 0
+                for it in per_param[i]:
+                    it[0] |= self.NO_DECAY
             self._per_param = per_param
             dev = a.data.device
             self._descs = torch.tensor(descs if descs else [[0] * 12], dtype=torch.int64, device=dev)
@@ -680,13 +786,13 @@ class FusedSGD(torch.optim.SGD):
             keep = [i for i in range(*rng) if i not in exclude]
             packs = [i for i in range(*rng) if i in pack_only]
             for i in packs:
-                if not self._per_param[i] or any(it[0] != 2 for it in self._per_param[i]):
+                if not self._per_param[i] or any(it[0] & 0xff != 2 for it in self._per_param[i]):
                     raise RuntimeError(f"parameter {i}: no elementwise re-pack layout")
             # conv re-pack items first (the heavier tiles start early), then elementwise items
             # (owner parameter, item) pairs; a re-pack-only item updates nothing: owner -1
-            own = [(i, it) for i in keep for it in self._per_param[i] if it[0] != 0] + \
+            own = [(i, it) for i in keep for it in self._per_param[i] if it[0] & 0xff != 0] + \
                   [(-1, [5] + it[1:]) for i in packs for it in self._per_param[i]] + \
-                  [(i, it) for i in keep for it in self._per_param[i] if it[0] == 0]
+                  [(i, it) for i in keep for it in self._per_param[i] if it[0] & 0xff == 0]
             sel = [it for _, it in own]
             if not sel and not exclude:
                 raise ValueError(f"no parameters in range {rng}")
@@ -698,10 +804,12 @@ class FusedSGD(torch.optim.SGD):
 
     def _elem_table(self, lo, hi):
         """Plain fp32 SGD items over arena elements [lo, hi) (no bf16 re-pack): the ZeRO-1
-        shard update (parallel/zero.py)."""
+        shard update (parallel/zero.py). Under the no-decay mask the chunks are cut where the
+        mask changes and the masked runs carry the flag."""
         t = self._elem_tables.get((lo, hi))
         if t is None:
-            items = [[0, s0, min(self.CHUNK, hi - s0), 0] for s0 in range(lo, hi, self.CHUNK)]
+            items = [[self.NO_DECAY if nd else 0, s0, min(self.CHUNK, e - s0), 0]
+                     for s, e, nd in self._decay_runs(lo, hi) for s0 in range(s, e, self.CHUNK)]
             if not items:
                 raise ValueError("empty element range")
             t = (torch.tensor(items, dtype=torch.int32, device=self.arena.data.device), len(items))
@@ -727,7 +835,12 @@ class FusedSGD(torch.optim.SGD):
             if lr_advance:
                 self.count_step()
             p, gr = a.data[lo:hi], a.grad[lo:hi]
-            d = gr.add(p, alpha=wd) if wd != 0 else gr
+            d = gr
+            if wd != 0:
+                d = gr.clone()
+                for s, e, nd in self._decay_runs(lo, hi):
+                    if not nd:
+                        d[s - lo:e - lo].add_(a.data[s:e], alpha=wd)
             if m != 0:
                 if not hasattr(self, "_flat_buf"):
                     self._flat_buf = torch.zeros_like(a.data)
@@ -748,6 +861,34 @@ class FusedSGD(torch.optim.SGD):
         items, n_items = self._elem_table(lo, hi)
         self._update_launch(items, n_items, s, zero_grad=zero_grad, counter=counter, skip=skip,
                             lr_advance=lr_advance)
+
+    def _cpu_masked_step(self, closure):
+        """CPU under the no-decay mask: torch.optim.SGD.step with the group taken as its two
+        sub-lists, the decayed parameters with ``weight_decay`` and the masked ones with 0 —
+        torch's own functional ``sgd`` both times, the momentum buffers in ``self.state`` in
+        torch's layout: bit for bit torch.optim.SGD with the two param groups."""
+        from torch.optim.sgd import sgd
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        for masked in (False, True):
+            sub = dict(g, params=[p for i, p in enumerate(g["params"])
+                                  if (i in self._no_decay) == masked],
+                       weight_decay=0.0 if masked else g["weight_decay"])
+            params, grads, bufs = [], [], []
+            sparse = self._init_group(sub, params, grads, bufs)
+            if not params:
+                continue
+            sgd(params, grads, bufs, weight_decay=sub["weight_decay"], momentum=g["momentum"],
+                lr=g["lr"], dampening=g["dampening"], nesterov=g["nesterov"],
+                maximize=g["maximize"], has_sparse_grad=sparse, foreach=g["foreach"],
+                fused=g["fused"], grad_scale=None, found_inf=None)
+            if g["momentum"] != 0:
+                for p, b in zip(params, bufs):
+                    self.state[p]["momentum_buffer"] = b
+        return loss
 
     def _descs_ptr(self):
         return self._work_table()[2].data_ptr()
@@ -829,7 +970,7 @@ class FusedSGD(torch.optim.SGD):
                         super().zero_grad(set_to_none=False)
                     return out
                 self._cpu_scale_grads(c)
-            out = super().step(closure)
+            out = self._cpu_masked_step(closure) if self._no_decay else super().step(closure)
             self._cpu_ema()
             if lr_advance:
                 self.count_step()
@@ -897,11 +1038,16 @@ class FusedSGD(torch.optim.SGD):
             # the EMA is switched on with the saved decay and seeded from the masters as they
             # are; its contents travel in the checkpoint (utils/misc.py ``ema_state_dict``)
             self.set_ema(saved["ema_decay"])
+        if "no_decay" in saved:
+            self.set_no_decay([int(i) for i in saved["no_decay"]])
+        mask = self.param_groups[0].get("no_decay")  # (a state dict without the key: as constructed)
         if not self._fused:
             out = super().load_state_dict({k: v for k, v in sd.items()
                                            if k not in ("lr_schedule", "grad_guard")})
             if self._ema_decay is not None:  # (an EMA that the saved groups do not know stays on)
                 self.param_groups[0]["ema_decay"] = self._ema_decay
+            if mask is not None:
+                self.param_groups[0]["no_decay"] = mask
             return out
         a = self.arena
         st = sd.get("state", {})

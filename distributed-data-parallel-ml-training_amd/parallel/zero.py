@@ -19,6 +19,8 @@ GPU: the pipelined step (engine/step.py SegmentedDDPStep(zero=True), ``bench.py 
 it per bucket on the comm stream. CPU (Gloo): the same sequence with torch.distributed
 (tests/test_zero_cpu.py).
 """
+import bisect
+
 import torch
 
 from ..optim.sgd import FusedSGD, launch_only_sharded
@@ -268,6 +270,12 @@ class ShardedBf16Update:
                 out.append((s, e, op))
         return out
 
+    def _masked(self, s):
+        """Arena element ``s`` belongs to a tensor under the optimizer's no-decay mask (padding
+        goes with the tensor before it)."""
+        nd = getattr(self.opt, "_no_decay", frozenset())
+        return bool(nd) and bisect.bisect_right(self.arena.offsets, s) - 1 in nd
+
     def _plan_bucket(self, j, slot_base):
         (_, (lo, hi)) = self.buckets[j]
         small = []  # per rank: list of (arena start, count, slot offset within the rank's row)
@@ -317,9 +325,11 @@ class ShardedBf16Update:
         items = []
         mine = {s: k for s, _, k in plan["small"][rank]}
         for s, e, op in self._pieces(s0, s1):
+            # (a piece lies in one tensor: a masked tensor's pieces run with wd = 0)
+            nd = FusedSGD.NO_DECAY if self._masked(s) else 0
             for c0 in range(s, e, FusedSGD.CHUNK):
                 c1 = min(e, c0 + FusedSGD.CHUNK)
-                items.append([3, c0, c1 - c0, -1 if op else mine[s] + (c0 - s)])
+                items.append([3 | nd, c0, c1 - c0, -1 if op else mine[s] + (c0 - s)])
         for a0, a1 in ((lo, s0), (s1, hi)):
             for c0 in range(a0, a1, 65536):
                 items.append([4, c0, min(a1, c0 + 65536) - c0, 0])
@@ -437,7 +447,9 @@ class ShardedBf16Update:
         p, gr, buf = self.master[s0:s1], a.grad[s0:s1], self.momentum[s0:s1]
         d = gr * gs if gs != 1.0 else gr.clone()
         if wd != 0:
-            d.add_(p, alpha=wd)
+            for s, e, _ in self._pieces(s0, s1):
+                if not self._masked(s):
+                    d[s - s0:e - s0].add_(p[s - s0:e - s0], alpha=wd)
         if m != 0:
             buf.mul_(m).add_(d)
             d = d.add(buf, alpha=m) if nesterov else buf

@@ -113,6 +113,11 @@ def build_parser(description=None, distributed=True):
                         'advanced once per optimizer step inside the update launch (works inside '
                         '--graph); a second evaluation pass runs on the averaged weights and '
                         '--save stores them as ema_state_dict; default 0 = off')
+    g.add_argument('--no-decay-1d', action='store_true',
+                   help='no weight decay on biases and BatchNorm gamma / beta (every parameter '
+                        'with dim() <= 1), the usual second param group of SGD, LARS, AdamW and '
+                        'LAMB recipes, decided per work item inside the update launch (works '
+                        'inside --graph); default off')
     return p
 
 
@@ -166,13 +171,16 @@ def optimizer_from_args(args, params, lr):
     AdamW(lr, (--adam-beta1, --adam-beta2), --adam-eps, 1e-2) with --optimizer adamw, or LAMB over
     AdamW's hyper-parameters with --optimizer lamb (biases and BatchNorm vectors are not adapted);
     --weight-decay replaces the optimizer's default decay; --clip-grad-norm /
-    --skip-nonfinite-grads switch the gradient guard of any of them on."""
+    --skip-nonfinite-grads switch the gradient guard of any of them on; --no-decay-1d takes the
+    decay off biases and BatchNorm vectors in any of them."""
     from ..optim import FusedSGD, LAMB, LARS, AdamW
     guard = {}
     if getattr(args, "clip_grad_norm", None) is not None or \
             getattr(args, "skip_nonfinite_grads", False):
         guard = {"max_grad_norm": getattr(args, "clip_grad_norm", None),
                  "skip_nonfinite": bool(getattr(args, "skip_nonfinite_grads", False))}
+    if getattr(args, "no_decay_1d", False):
+        guard = dict(guard, no_decay="1d")
     wd = getattr(args, "weight_decay", None)
     if getattr(args, "optimizer", "sgd") in ("adamw", "lamb"):
         cls = LAMB if args.optimizer == "lamb" else AdamW
