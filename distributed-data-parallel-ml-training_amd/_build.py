@@ -49,6 +49,11 @@ VARIANTS = {"release": ("_native", "native", []),
             "stamps": ("_native_stamps", "native_stamps", ["-DDDP_CONV_STAMPS"])}
 
 
+# per-source device flags: linear_wide.hip is compiled without the packed fp32 VALU forms
+# (v_pk_{add,mul,fma}_f32); the other translation units keep the flags they were tuned with
+EXTRA_FLAGS = {"linear_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def ext_path(variant="release"):
     suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     return os.path.join(PKG_DIR, VARIANTS[variant][0] + suffix)
@@ -130,7 +135,8 @@ def _build_variant(variant, verbose=True, jobs=None):
     tasks = []
     for src in sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip"))):
         obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-x", "hip", *common, *inc, "-c", src, "-o", obj,
+        cmd = [hipcc, f"--offload-arch={ARCH}", "-x", "hip", *common,
+               *EXTRA_FLAGS.get(os.path.basename(src), []), *inc, "-c", src, "-o", obj,
                "-MMD", "-MF", obj + ".d"]
         tasks.append((cmd, src, obj))
     host_srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp"))) + [os.path.join(CSRC, "bind.cpp")]

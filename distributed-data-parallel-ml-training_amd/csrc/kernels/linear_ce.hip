@@ -12,9 +12,11 @@
 //        (both in one launch; g is read from device memory: autograd's incoming gradient)
 // The Linear weight is read straight from the fp32 master copy (20 KB).
 // A separate generic softmax-CE (any J, logits from the MFMA GEMM) serves ResNet-50's 1000-way head.
+// 16 < J <= 128 (CIFAR-100): the entry points below route to the MFMA head, linear_wide.hip.
 #include "common.h"
 #include "api.h"
 #include "linear_blocks.h"
+#include "linear_wide.h"
 
 namespace ddp_amd {
 
@@ -25,33 +27,7 @@ namespace ddp_amd {
 // 0 writes the [6][F] table its backward reads), each lane applies BN + ReLU to its 8 channels
 // of the four window pixels, max-pools them (bn_act.hip's rule) and stores the bf16 feature,
 // which then feeds the dot products exactly as a loaded x would.
-constexpr int kMaxHeadF = 1024;
-
-// Soft targets (api.h SoftTarget; label smoothing E and mixup partner yb with weight lam) of one
-// row, as the SOFT instantiations of both loss kernels evaluate them:
-//   t_j       = fma(1 - E, wa [j == ya] + wb [j == yb], E / J)
-//   loss term = fma(E / J, sum_j z_j, (1 - E) * fma(wa, z_ya, wb * z_yb))
-// with (wa, wb) = (lam, 1 - lam), or (1, 0) when yb == ya (lam + (1 - lam) is 1 without a
-// rounding). E = 0, lam = 1 or yb == ya gives t = onehot(ya) and the term z_ya, bit for bit.
-struct SoftRow {
-  float om, u, wa, wb;  // 1 - E, E / J, the two label weights
-  int yb;
-  __device__ __forceinline__ SoftRow(const SoftTarget& s, int row, int ya, int J) {
-    const float lam = s.lam ? *s.lam : 1.f;
-    yb = s.labels_b ? (int)s.labels_b[row] : ya;
-    om = 1.f - s.smoothing;
-    u = s.smoothing / (float)J;
-    wa = yb == ya ? 1.f : lam;
-    wb = yb == ya ? 0.f : 1.f - lam;
-  }
-  __device__ __forceinline__ float target(int j, int ya) const {
-    return __builtin_fmaf(om, (j == ya ? wa : 0.f) + (j == yb ? wb : 0.f), u);
-  }
-  __device__ __forceinline__ float term(float z_ya, float z_yb, float sum_z) const {
-    return __builtin_fmaf(u, sum_z, om * __builtin_fmaf(wa, z_ya, wb * z_yb));
-  }
-};
-__device__ __forceinline__ const SoftTarget& only(const SoftTarget& s) { return s; }
+// (kMaxHeadF, and the soft-target rule SoftRow of the SOFT instantiations: linear_wide.h)
 
 // SOFT: ``soft`` = one SoftTarget, passed to the soft instantiations only (the plain ones keep
 // their argument list); everything soft sits under ``if constexpr (SOFT)``.
@@ -317,7 +293,10 @@ extern "C" int ddp_linear_ce_fwd(const void* x, const float* W, const float* b,
                                  const long long* labels, int B, int F, int J, float* logits,
                                  float* dlogits, float* loss_sum, int* correct, float* loss_acc,
                                  hipStream_t st) {
-  if (J > kMaxJ || F % 8) return -1;
+  if (J > kMaxJ)
+    return linear_wide_fwd(x, W, b, labels, B, F, J, logits, dlogits, loss_sum, correct, loss_acc,
+                           nullptr, st);
+  if (F % 8) return -1;
   hipLaunchKernelGGL((linear_ce_fwd_kernel<false, false>), dim3((B + 3) / 4), dim3(256), 0, st,
                      (const unsigned short*)x, W, b, labels, B, F, J, 1.f / (float)B, logits,
                      dlogits, loss_sum, correct, loss_acc, HeadBnIn{});
@@ -347,7 +326,12 @@ extern "C" int ddp_linear_ce_fwd_soft(const HeadBnIn* bn, const void* x, const f
                                       const float* b, const long long* labels, int B, int F, int J,
                                       float* logits, float* dlogits, float* loss_sum, int* correct,
                                       float* loss_acc, const SoftTarget* soft, hipStream_t st) {
-  if (J > kMaxJ || F % 8 || !soft_ok(soft, labels)) return -1;
+  if (!soft_ok(soft, labels)) return -1;
+  if (J > kMaxJ)  // the wide head reads stored features: the last block is never folded in
+    return bn ? -1
+              : linear_wide_fwd(x, W, b, labels, B, F, J, logits, dlogits, loss_sum, correct,
+                                loss_acc, soft, st);
+  if (F % 8) return -1;
   if (bn) {
     if (F > kMaxHeadF || !bn->z || !bn->stats || !bn->gamma || !bn->beta || !bn->coef || !bn->y)
       return -1;
@@ -366,7 +350,8 @@ extern "C" int ddp_linear_ce_fwd_soft(const HeadBnIn* bn, const void* x, const f
 extern "C" int ddp_linear_bwd(const float* dlogits, const void* x, const float* W, int B, int F,
                               int J, const float* gscale, void* dx, float* dW, float* db,
                               hipStream_t st) {
-  if (J > kMaxJ || F % 8) return -1;
+  if (J > kMaxJ) return linear_wide_bwd(dlogits, x, W, B, F, J, gscale, dx, dW, db, st);
+  if (F % 8) return -1;
   const int ndx = dx ? (B + 3) / 4 : 0;
   const int nfx = (F + 63) / 64, nry = (B + kDwRows - 1) / kDwRows;
   hipLaunchKernelGGL(linear_bwd_kernel, dim3(ndx + nfx * nry), dim3(256), 0, st, dlogits,

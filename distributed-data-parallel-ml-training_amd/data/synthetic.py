@@ -93,6 +93,14 @@ def SyntheticCIFAR10(train=True, seed=89395, n=None):
                                  name="cifar10-train" if train else "cifar10-test")
 
 
+def SyntheticCIFAR100(train=True, seed=89395, n=None, classes=100):
+    """CIFAR-100-shaped: CIFAR-10's image shape and set sizes with 100 classes (``classes``: any
+    other count over the same images, the mains' --num-classes)."""
+    n = n if n is not None else (50000 if train else 10000)
+    return SyntheticImageDataset(n, 32, 32, classes, seed if train else seed + 1,
+                                 name=f"cifar{classes}-train" if train else f"cifar{classes}-test")
+
+
 def SyntheticImageNet(train=True, seed=89395, n=None, size=224):
     """ImageNet-shaped: 3x224x224, 1000 classes (driver's ResNet-50 config)."""
     n = n if n is not None else (2048 if train else 512)

@@ -15,7 +15,7 @@ import os
 import torch
 
 from .. import SEED
-from ..data import SyntheticCIFAR10, make_loader
+from ..data import SyntheticCIFAR10, SyntheticCIFAR100, make_loader
 from ..models import build
 from ..parallel import (DistributedDataParallel, STRATEGIES, destroy, init_distributed_setup,
                         make_communicator, test_distributed_setup)
@@ -45,14 +45,20 @@ def main(part, argv=None):
     batch_size = int(args.global_batch / world)  # batch for one node
 
     criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)  # --label-smoothing
-    train_ds = SyntheticCIFAR10(train=True, seed=SEED, n=args.train_size)
-    test_ds = SyntheticCIFAR10(train=False, seed=SEED, n=args.test_size)
+    # --num-classes (opt-in): the dataset's class count and the model's head; 10 = the reference
+    nc = args.num_classes
+    if nc == 10:
+        train_ds = SyntheticCIFAR10(train=True, seed=SEED, n=args.train_size)
+        test_ds = SyntheticCIFAR10(train=False, seed=SEED, n=args.test_size)
+    else:
+        train_ds = SyntheticCIFAR100(train=True, seed=SEED, n=args.train_size, classes=nc)
+        test_ds = SyntheticCIFAR100(train=False, seed=SEED, n=args.test_size, classes=nc)
     train_loader = make_loader(train_ds, batch_size, device, world, rank, train=True,
                                shard=distributed, max_batches=args.max_batches,
                                mixup_alpha=args.mixup_alpha)  # --mixup-alpha
     test_loader = make_loader(test_ds, batch_size, device, train=False, shard=False)
 
-    model = build(args.model).to(device)
+    model = build(args.model, None if nc == 10 else nc).to(device)
     comm = make_communicator(device) if distributed else None
     if strategy == "ddp":
         # --graph on a GPU captures the step (TrainStep: inline collectives, one bucket is
@@ -78,7 +84,7 @@ def main(part, argv=None):
     sync = None
     if strategy in STRATEGIES:
         sync = functools.partial(_sync, STRATEGIES[strategy], comm)
-    metrics = MetricsSink(args.metrics, rank)
+    metrics = MetricsSink(args.metrics, rank, extra={} if nc == 10 else {"num_classes": nc})
     # failure detection (the reference has none, part2/part2a/main.py:58): beat
     # once per iteration; no beat for --watchdog-s seconds or an RCCL async error -> abort the
     # communicator and exit non-zero instead of hanging on a dead peer

@@ -1,8 +1,9 @@
-"""VGG family (VGG-11/13/16/19) for 3x32x32 inputs and 10 classes.
+"""VGG family (VGG-11/13/16/19) for 3x32x32 inputs; 10 classes by default (``num_classes``:
+up to 128 on the GPU, e.g. 100 for CIFAR-100).
 
 Reference parity: part1/model.py:3-50 (identical copies in part2/part2a, part2/part2b, part3).
 The module tree — ``layers`` (nn.Sequential of Conv2d(3x3,s1,p1,bias) / BatchNorm2d(
-track_running_stats=False) / ReLU(inplace) / MaxPool2d(2,2)) and ``fc1`` (Linear(512, 10)) —
+track_running_stats=False) / ReLU(inplace) / MaxPool2d(2,2)) and ``fc1`` (Linear(512, classes)) —
 is kept exactly so that ``state_dict`` keys and shapes match the reference checkpoint layout
 (``layers.{0,4,8,...}.{weight,bias}``, BN without running buffers, ``fc1.{weight,bias}``).
 
@@ -10,7 +11,7 @@ Execution:
 * CPU tensors run the ATen modules unchanged (the numerical oracle, and the part1 CPU path).
 * GPU tensors run the fused gfx950 path: each Conv->BN->ReLU(->MaxPool) group becomes one
   ``ConvBNAct`` autograd Function (ops/layers.py), activations stay NHWC bf16, the head is a
-  fused small-Linear kernel. Inputs may be NCHW fp32 (converted on device) or the NHWC bf16
+  fused Linear + loss kernel (one wave per row up to 16 classes, the MFMA head up to 128). Inputs may be NCHW fp32 (converted on device) or the NHWC bf16
   batches produced by the on-device data pipeline (data/loader.py).
 """
 import torch
@@ -43,7 +44,7 @@ def _make_layers(cfg):
 
 
 class _VGG(nn.Module):
-    """VGG module for 3x32x32 input, 10 classes."""
+    """VGG module for 3x32x32 input, ``num_classes`` classes (default 10)."""
 
     def __init__(self, name, num_classes=10):
         super().__init__()
@@ -169,9 +170,11 @@ class _VGG(nn.Module):
             if acc is not None:
                 acc.add_(loss.detach())
             return loss
-        from ..ops.layers import linear_cross_entropy
+        from ..ops.layers import HEAD_NARROW_MAX, linear_cross_entropy
         last = self.fused_plan()[-1]
-        last.defer_to_head = True  # its BN + ReLU + pool may run inside the head's kernel
+        # its BN + ReLU + pool may run inside the narrow head's kernel; the wide head (more than 16
+        # classes) reads stored features, so the block then runs its own pass
+        last.defer_to_head = self.fc1.weight.shape[0] <= HEAD_NARROW_MAX
         try:
             h = self._features_fused(x)
         finally:
@@ -179,17 +182,17 @@ class _VGG(nn.Module):
         return linear_cross_entropy(h, self.fc1, labels, acc, transient, bn_prev=last, soft=soft)
 
 
-def VGG11():
-    return _VGG('VGG11')
+def VGG11(num_classes=10):
+    return _VGG('VGG11', num_classes)
 
 
-def VGG13():
-    return _VGG('VGG13')
+def VGG13(num_classes=10):
+    return _VGG('VGG13', num_classes)
 
 
-def VGG16():
-    return _VGG('VGG16')
+def VGG16(num_classes=10):
+    return _VGG('VGG16', num_classes)
 
 
-def VGG19():
-    return _VGG('VGG19')
+def VGG19(num_classes=10):
+    return _VGG('VGG19', num_classes)

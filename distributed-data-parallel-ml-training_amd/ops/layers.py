@@ -730,7 +730,8 @@ def conv_bn_act(x, spec, residual=None, in_link=None, res_link=None, res_bn=None
 
 # ------------------------------------------------------------------ classifier head
 class _LinearSmallFn(torch.autograd.Function):
-    """Linear with few outputs (J <= 16): bf16 [B, F] -> fp32 logits [B, J]."""
+    """Linear with few outputs (J <= 128; the wide MFMA head above 16): bf16 [B, F] -> fp32
+    logits [B, J]."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -780,7 +781,7 @@ class _LinearCEFn(torch.autograd.Function):
         loss = (step_scratch(x.device).take_transient(1).view(()) if transient
                 else torch.zeros((), dtype=F32, device=x.device))
         dl = torch.empty(B, J, dtype=F32, device=x.device)
-        if (bn_prev is not None and bn_prev.deferred is not None
+        if (J <= HEAD_NARROW_MAX and bn_prev is not None and bn_prev.deferred is not None
                 and bn_prev.deferred.data_ptr() == x.data_ptr() and ctx.prev_z is not None):
             # the last block deferred its BN + ReLU + pool here: x is written by this kernel
             bn_prev.deferred = None
@@ -807,8 +808,8 @@ class _LinearCEFn(torch.autograd.Function):
         gb = ensure_grad(bias) if bias is not None else None
         prev, pz = ctx.bn_prev, ctx.prev_z
         ctx.prev_z = None
-        if (prev is not None and pz is not None and ctx.needs_input_grad[0] and BN_BWD_APPLY_FUSE
-                and HEAD_BN_FUSE
+        if (J <= HEAD_NARROW_MAX and prev is not None and pz is not None
+                and ctx.needs_input_grad[0] and BN_BWD_APPLY_FUSE and HEAD_BN_FUSE
                 and _common.BN_BWD_FUSE and prev.pool and not prev.residual
                 and pz.shape[1] == 2 and pz.shape[2] == 2 and prev.K == F):
             dz_prev = torch.empty_like(pz)
@@ -828,19 +829,32 @@ class _LinearCEFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
+# The head kernels (csrc/kernels/linear_ce.hip, linear_wide.hip): one wave per row up to
+# HEAD_NARROW_MAX outputs (the only design the last block's BatchNorm folds into), the MFMA head
+# up to HEAD_WIDE_MAX outputs over a feature count that is a multiple of 32, at most 1024.
+HEAD_NARROW_MAX = 16
+HEAD_WIDE_MAX = 128
+
+
+def _check_head(name, linear):
+    J, F = linear.weight.shape
+    if J > HEAD_WIDE_MAX or (J > HEAD_NARROW_MAX and (F % 32 or F > 1024)):
+        raise ValueError(f"{name} supports at most {HEAD_NARROW_MAX} outputs, or up to "
+                         f"{HEAD_WIDE_MAX} over a multiple of 32 features <= 1024 "
+                         f"(got {J} outputs, {F} features)")
+
+
 def linear_cross_entropy(x, linear, labels, acc=None, transient=False, bn_prev=None, soft=None):
-    """mean CE(linear(x), labels) in one kernel (J <= 16); see _LinearCEFn. ``transient=True``
+    """mean CE(linear(x), labels) in one kernel (J <= 128); see _LinearCEFn. ``transient=True``
     returns the loss in the per-forward scratch (saves a fill launch; valid until the next
     model forward on this device — the captured training step uses it). ``soft``: a SoftTarget
     (label smoothing / mixup) in place of the one-hot target."""
-    if linear.weight.shape[0] > 16:
-        raise ValueError("linear_cross_entropy supports at most 16 outputs")
+    _check_head("linear_cross_entropy", linear)
     return _LinearCEFn.apply(x, linear.weight, linear.bias, labels, acc, transient, bn_prev, soft)
 
 
 def linear_small(x, linear):
-    if linear.weight.shape[0] > 16:
-        raise ValueError("linear_small supports at most 16 outputs")
+    _check_head("linear_small", linear)
     return _LinearSmallFn.apply(x, linear.weight, linear.bias)
 
 

@@ -39,6 +39,11 @@ def build_parser(description=None, distributed=True):
     g = p.add_argument_group("ddp_amd extensions (opt-in; reference defaults unchanged)")
     g.add_argument('--device', default='auto', help='auto | cpu | cuda')
     g.add_argument('--model', default='vgg11', help='vgg11 | vgg13 | vgg16 | vgg19 | resnet50')
+    g.add_argument('--num-classes', type=_num_classes, default=10,
+                   help="classes of the synthetic CIFAR-shaped dataset and outputs of the model's "
+                        'head (100 = CIFAR-100); a VGG on the GPU serves up to 16 with the '
+                        'one-wave-per-row head and 17..128 with the MFMA head (works inside '
+                        '--graph); default 10')
     g.add_argument('--epochs', type=int, default=1)
     g.add_argument('--global-batch', type=int, default=256, help='split int(B/world) per rank')
     g.add_argument('--train-size', type=int, default=None, help='synthetic train-set size')
@@ -119,6 +124,13 @@ def build_parser(description=None, distributed=True):
                         'LAMB recipes, decided per work item inside the update launch (works '
                         'inside --graph); default off')
     return p
+
+
+def _num_classes(v):
+    n = int(v)
+    if n < 2:
+        raise argparse.ArgumentTypeError("--num-classes must be >= 2")
+    return n
 
 
 def _adam_beta(v):

@@ -52,14 +52,17 @@ def pick_device(spec="auto", local_rank=None):
 
 
 class MetricsSink:
-    """Append-only JSON-lines metrics file (no-op when path is None)."""
+    """Append-only JSON-lines metrics file (no-op when path is None). ``extra``: fields every
+    record gains (the run's non-default settings, e.g. num_classes)."""
 
-    def __init__(self, path=None, rank=0):
-        self.path, self.rank = path, rank
+    def __init__(self, path=None, rank=0, extra=None):
+        self.path, self.rank, self.extra = path, rank, dict(extra or {})
 
     def log(self, **kv):
         if not self.path:
             return
+        for k, v in self.extra.items():
+            kv.setdefault(k, v)
         kv.setdefault("ts", time.time())
         kv.setdefault("rank", self.rank)
         with open(self.path, "a") as f:
