@@ -591,7 +591,7 @@ PYBIND11_MODULE(_native, m) {
                        uintptr_t adam_v, uintptr_t adam_bias, unsigned adam_n_bias,
                        float adam_omb1, float adam_beta2, float adam_omb2, float adam_eps,
                        uintptr_t lamb_side, uintptr_t lamb_tensors, uintptr_t lamb_partial,
-                       uintptr_t lamb_trust) {
+                       uintptr_t lamb_trust, uintptr_t muon_side, uintptr_t muon_tensors) {
     ddp_amd::UpdateLaunch u{};
     u.items = P<int4>(items); u.descs = P<ddp_amd::ConvDesc>(descs);
     u.p = P<float>(p); u.g = P<float>(g); u.buf = P<float>(buf);
@@ -608,6 +608,7 @@ PYBIND11_MODULE(_native, m) {
               adam_omb2, adam_eps};
     u.lamb = {P<int2>(lamb_side), P<int4>(lamb_tensors), P<float2>(lamb_partial),
               P<float>(lamb_trust)};
+    u.muon = {P<const int>(muon_side), P<const ddp_amd::MuonTensor>(muon_tensors)};
     check(ddp_sgd_pack(&u, S(st)), "sgd_pack");
   }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("p"), py::arg("g"),
      py::arg("buf"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("grad_scale"),
@@ -622,7 +623,34 @@ PYBIND11_MODULE(_native, m) {
      py::arg("adam_v") = 0, py::arg("adam_bias") = 0, py::arg("adam_n_bias") = 0,
      py::arg("adam_omb1") = 0.f, py::arg("adam_beta2") = 0.f, py::arg("adam_omb2") = 0.f,
      py::arg("adam_eps") = 0.f, py::arg("lamb_side") = 0, py::arg("lamb_tensors") = 0,
-     py::arg("lamb_partial") = 0, py::arg("lamb_trust") = 0);
+     py::arg("lamb_partial") = 0, py::arg("lamb_trust") = 0, py::arg("muon_side") = 0,
+     py::arg("muon_tensors") = 0);
+  // Muon's stage launch (muon.hip muon_stage_kernel, api.h MuonStage): bf16(d) into the staging
+  // matrices and per-chunk sum d^2; clip_* select the guarded instantiation
+  m.def("muon_stage", [](uintptr_t items, int n_items, uintptr_t tensors, uintptr_t g, uintptr_t m,
+                         float mu, float grad_scale, int nesterov, uintptr_t partial, uintptr_t st,
+                         uintptr_t clip_partial, int clip_chunks, float clip_max_norm,
+                         float clip_eps, int clip_flags) {
+    ddp_amd::MuonStage s{};
+    s.items = P<int4>(items); s.n_items = n_items;
+    s.tensors = P<const ddp_amd::MuonTensor>(tensors);
+    s.g = P<float>(g); s.m = P<float>(m); s.mu = mu; s.grad_scale = grad_scale;
+    s.nesterov = nesterov; s.partial = P<float>(partial);
+    s.clip = {P<const float>(clip_partial), clip_chunks, clip_max_norm, clip_eps, clip_flags,
+              nullptr};
+    check(ddp_muon_stage(&s, S(st)), "muon_stage");
+  }, py::arg("items"), py::arg("n_items"), py::arg("tensors"), py::arg("g"), py::arg("m"),
+     py::arg("mu"), py::arg("grad_scale"), py::arg("nesterov"), py::arg("partial"),
+     py::arg("stream"), py::arg("clip_partial") = 0, py::arg("clip_chunks") = 0,
+     py::arg("clip_max_norm") = 0.f, py::arg("clip_eps") = 0.f, py::arg("clip_flags") = 0);
+  // one grouped Newton-Schulz GEMM launch (muon.hip muon_gemm_kernel, api.h MuonGemm): int4 tile
+  // items {desc row, tile row, tile column, mirror}; nn = 0: A B^T, 1: A B
+  m.def("muon_gemm", [](uintptr_t items, int n_items, uintptr_t descs, uintptr_t partial, int nn,
+                        uintptr_t st) {
+    check(ddp_muon_gemm(P<void>(items), n_items, P<const ddp_amd::MuonGemm>(descs),
+                        P<const float>(partial), nn, S(st)), "muon_gemm");
+  }, py::arg("items"), py::arg("n_items"), py::arg("descs"), py::arg("partial"), py::arg("nn"),
+     py::arg("stream"));
   // gradient guard (optim.hip chunk_sums_kernel<false>): per-chunk sum (g * grad_scale)^2 of every
   // parameter chunk in the items, the input of sgd_pack's clip_* arguments
   m.def("grad_sumsq", [](uintptr_t items, int n_items, uintptr_t g, float grad_scale,

@@ -344,6 +344,74 @@ struct LambNorms {
   ClipArgs clip;          // optional: clip.partial == null
 };
 
+// Muon (optim/muon.py; momentum orthogonalised by a Newton-Schulz iteration). One orthogonalised
+// tensor as the stage kernel and the update launch see it: the fp32 arena tensor at ``p_offset``
+// is the matrix [K][rest] (element e: row e / rest, column e % rest), its bf16 staging matrix
+// ``x`` is always wide, ``pitch`` elements per row, both dimensions zero-padded to multiples of
+// 32: element (r, c) lives at x[r * pitch + c], or at x[c * pitch + r] when ``transposed``
+// (K > rest). Stage: x = X0, written. Update: x = O (the last iterate), read; ``scale`` =
+// float32(sqrt(max(1, K / rest))).
+struct MuonTensor {
+  long long p_offset;
+  unsigned short* x;
+  int pitch, rest, transposed;
+  float scale;
+};
+static_assert(sizeof(MuonTensor) == 32, "MuonTensor is a 32-byte table row");
+
+// The stage launch (muon.hip muon_stage_kernel): one block per chunk item {arena offset, count
+// <= 8192, global chunk, row of ``tensors``} of the orthogonalised tensors forms
+//     G = g * gs;  m' = fma(mu, m, G);  d = nesterov ? fma(mu, m', G) : m'
+// in registers, stores neither m' nor p, writes bf16(d) into the tensor's staging matrix and
+// sum d^2 into ``partial[global chunk]`` (plain stores). ``clip.partial`` non-null: gs is
+// grad_scale times the guard's clip coefficient, as in LambNorms.
+struct MuonStage {
+  const int4* items;
+  int n_items;
+  const MuonTensor* tensors;
+  const float* g;
+  const float* m;
+  float mu, grad_scale;
+  int nesterov;
+  float* partial;
+  ClipArgs clip;          // optional: clip.partial == null
+};
+
+// One GEMM of a grouped launch (muon.hip muon_gemm_kernel), 80 bytes in device memory:
+//     D = bf16(alpha' * (A op B) + beta' * E)        fp32 accumulation, E optional (null)
+// NT: op = A B^T, both operands [row][k]; NN: op = A B, B [k][col]. Every dimension is a multiple
+// of 32 (``ksteps`` = reduction length / 32) and D has ``ldd`` elements per row, as E. Elements
+// of D outside ``rows`` x ``cols`` are stored as +0 (the zero padding stays zero whatever the
+// arithmetic gave). ``norm_n`` > 0: the block sums partial[norm0 .. norm0 + norm_n) in the fixed
+// order of the trust ratios (lane l adds chunks l, l + 64, ...; wave_sum), s0 = 1 / (sqrt(S) +
+// 1e-7), and alpha' = alpha * s0^alpha_pow, beta' = beta * s0^beta_pow (one fp32 product per
+// power, alpha first); else alpha' = alpha, beta' = beta.
+// Work items: int4 {row of the desc table, tile row, tile column, mirror}: one 32 x 32 tile of D;
+// mirror != 0 on an off-diagonal tile of a symmetric product also stores the transposed tile.
+struct MuonGemm {
+  const unsigned short* a;
+  const unsigned short* b;
+  const unsigned short* e;
+  unsigned short* d;
+  int lda, ldb, ldd, ksteps;
+  float alpha, beta;
+  int norm0, norm_n;
+  int alpha_pow, beta_pow;
+  int rows, cols;
+};
+static_assert(sizeof(MuonGemm) == 80, "MuonGemm is an 80-byte table row");
+
+// Muon in the update launch: ``side`` non-null selects the MUON instantiations (not with LARS or
+// AdamW). An item whose kind word carries bit 9 belongs to an orthogonalised tensor, row
+// side[item] of ``tensors`` (x = O); its elements take
+//     m' as the stage kernel formed it (common.h muon_dir), stored
+//     p' = fma(-(lr * scale), O, fma(-(lr * wd), p, p))
+// and every other item SgdHyper's momentum rule as it is.
+struct MuonArgs {
+  const int* side;            // per work item: row of ``tensors`` (read only under bit 9)
+  const MuonTensor* tensors;
+};
+
 struct UpdateLaunch {
   const int4* items;      // work items, kinds 0-5 (optim.hip), one block each; kind word | 0x100
                           // on an updating item: SgdHyper::wd is 0 for that block
@@ -358,6 +426,7 @@ struct UpdateLaunch {
   EmaArgs ema;            // optional: ema.ema == null
   AdamArgs adam;          // optional: adam.v == null
   LambArgs lamb;          // optional: lamb.side == null
+  MuonArgs muon;          // optional: muon.side == null
 };
 
 struct AugArgs {
@@ -535,7 +604,7 @@ void ddp_conv_stamps_set(void* buf, int cap);
 int ddp_pack_conv_weights(const ddp_amd::PackDesc* descs, int n, hipStream_t st);
 // the fused SGD + re-pack launch (UpdateLaunch above); -1: a LARS pointer or clip.stats missing,
 // or AdamW with LARS, without its bias table or without a schedule, or LAMB without AdamW, with
-// LARS or with one of its pointers missing
+// LARS or with one of its pointers missing, or Muon with LARS, AdamW or without its tensor table
 int ddp_sgd_pack(const ddp_amd::UpdateLaunch* u, hipStream_t st);
 // the two per-chunk sums: int4 items {arena offset, count <= 8192, global chunk, -}, one block
 // each; ``partial`` as ClipArgs::partial (float) and LarsArgs::partial (float2)
@@ -546,6 +615,11 @@ int ddp_lars_norms(const void* items, int n_items, const float* p, const float* 
 // LAMB's per-chunk {sum p^2, sum r^2} (LambNorms); -1: a pointer, the bias table or the schedule
 // is missing
 int ddp_lamb_norms(const ddp_amd::LambNorms* n, hipStream_t st);
+// Muon's stage launch (MuonStage); -1: a pointer is missing
+int ddp_muon_stage(const ddp_amd::MuonStage* s, hipStream_t st);
+// one grouped GEMM launch over ``n_items`` tile items (MuonGemm); nn: 0 = A B^T, 1 = A B
+int ddp_muon_gemm(const void* items, int n_items, const ddp_amd::MuonGemm* descs,
+                  const float* partial, int nn, hipStream_t st);
 // tail of a pipelined step with sharded buckets: gathered small-tensor slots -> fp32 arena,
 // re-pack of channel-padded conv operands, then release-increment ``signal`` (optim.hip)
 int ddp_shard_tail(const void* segs, int n_segs, const float* src, float* dst,

@@ -137,6 +137,45 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(lane_f(v, 0), lane_f(v, 16)), fmaxf(lane_f(v, 32), lane_f(v, 48)));
 }
 
+// The guard's verdict of this step, the same in every block of the launch.
+struct GuardState {
+  float norm, c;  // sqrt(sum (g * grad_scale)^2) over every parameter element; clip coefficient
+  int skipped;    // non-finite norm with skip_nonfinite: the launch only clears the gradients
+  float* stats;   // ClipArgs::stats
+  int count;      // this launch ends the step: a skipped step is counted
+};
+
+__device__ __forceinline__ GuardState clip_block(const ClipArgs& a) {
+  __shared__ float s_norm, s_c;
+  __shared__ int s_skipped;
+  if (threadIdx.x < 64) {
+    float s = 0.f;
+    for (int c = threadIdx.x; c < a.n_chunks; c += 64) s += a.partial[c];
+    const float norm = sqrtf(wave_sum(s));
+    float c = 1.f;
+    if (a.flags & 1) {
+      const float q = a.max_norm / (norm + a.eps);
+      c = q >= 1.f ? 1.f : q;  // a NaN norm gives a NaN coefficient, as the arithmetic says
+    }
+    if (threadIdx.x == 0) {
+      s_norm = norm;
+      s_c = c;
+      s_skipped = ((a.flags & 2) && !(norm <= 3.402823466e+38f)) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  return GuardState{s_norm, s_c, s_skipped, a.stats, (a.flags & 4) ? 1 : 0};
+}
+
+// Muon's momentum step of one element (optim/muon.py; api.h MuonStage): the new momentum into m,
+// returns the direction d that is orthogonalised. The stage kernel (muon.hip) and the MUON items
+// of the update launch (optim.hip) both form m' through this, so the two passes give the same bits.
+__device__ __forceinline__ float muon_dir(float g, float& m, float gs, float mu, int nesterov) {
+  const float G = g * gs;
+  m = __builtin_fmaf(mu, m, G);
+  return nesterov ? __builtin_fmaf(mu, m, G) : m;
+}
+
 // Bijective XCD-aware block remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"):
 // consecutive logical tiles land on the same XCD (shared L2) instead of round-robin.
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {

@@ -11,7 +11,9 @@
 // decay instead: the momentum arena holds the first moment, one more arena the second, and the
 // bias corrections of the step come from a device table next to the learning rate's. With LAMB
 // (optim/lamb.py, api.h LambArgs) a norms launch over p, g, m, v runs in front (lamb_norms_kernel)
-// and the same launch scales every adapted tensor's AdamW-style update by |w| / |update|.
+// and the same launch scales every adapted tensor's AdamW-style update by |w| / |update|. With Muon
+// (optim/muon.py, api.h MuonArgs) the stage launch and the Newton-Schulz GEMMs of muon.hip run in
+// front and the items of the orthogonalised tensors apply the orthogonalised momentum instead.
 //
 // pack_conv_weights re-lays the fp32 master weights (PyTorch [K][C][R][S]) into the two bf16
 // MFMA operand layouts used by conv_igemm.hip: Wc [K][R][S][Cpad] (fwd) and Wt [C][R][S][K]
@@ -120,12 +122,14 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(PackTable t) {
 // The kind is the low byte of the first word. Bit 8 (kItemNoDecay) on an updating item (kinds
 // 0-3): its tensor is not weight-decayed (optim/sgd.py ``no_decay``) — the block runs the same
 // rule with wd = 0, taken once per block in front of the prologues that use it. Never set on
-// kinds 4 and 5.
+// kinds 4 and 5. Bit 9 (kItemMuon, MUON instantiations only) on an item of kind 0, 1 or 2: its
+// tensor is orthogonalised (api.h MuonArgs).
 // Conv descriptors: api.h ConvDesc. Arguments: api.h SgdHyper, LarsArgs, ClipArgs, EmaArgs,
 // AdamArgs, LambArgs.
 constexpr int kTileElems = 9216;  // fp32 LDS tile (36 KB)
 constexpr int kItemKindMask = 0xff;
 constexpr int kItemNoDecay = 0x100;
+constexpr int kItemMuon = 0x200;
 
 __device__ __forceinline__ int item_kind(const int4& it) { return it.x & kItemKindMask; }
 
@@ -531,34 +535,38 @@ __device__ __forceinline__ float lamb_trust_block(const LambArgs& a) {
   return s_trust;
 }
 
-// The guard's verdict of this step, the same in every block of the launch.
-struct GuardState {
-  float norm, c;  // sqrt(sum (g * grad_scale)^2) over every parameter element; clip coefficient
-  int skipped;    // non-finite norm with skip_nonfinite: the launch only clears the gradients
-  float* stats;   // ClipArgs::stats
-  int count;      // this launch ends the step: a skipped step is counted
-};
+// (GuardState and clip_block, the guard's verdict in a block's prologue: common.h)
 
-__device__ __forceinline__ GuardState clip_block(const ClipArgs& a) {
-  __shared__ float s_norm, s_c;
-  __shared__ int s_skipped;
-  if (threadIdx.x < 64) {
-    float s = 0.f;
-    for (int c = threadIdx.x; c < a.n_chunks; c += 64) s += a.partial[c];
-    const float norm = sqrtf(wave_sum(s));
-    float c = 1.f;
-    if (a.flags & 1) {
-      const float q = a.max_norm / (norm + a.eps);
-      c = q >= 1.f ? 1.f : q;  // a NaN norm gives a NaN coefficient, as the arithmetic says
-    }
-    if (threadIdx.x == 0) {
-      s_norm = norm;
-      s_c = c;
-      s_skipped = ((a.flags & 2) && !(norm <= 3.402823466e+38f)) ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  return GuardState{s_norm, s_c, s_skipped, a.stats, (a.flags & 4) ? 1 : 0};
+// MUON: the block's orthogonalised tensor (``on``: the item carries kItemMuon) and its two
+// products, once per block. MUON = false: an empty argument and no code.
+struct NoMuon {};
+struct MuonItem {
+  bool on;
+  MuonTensor t;
+  float nls, nlw;  // -(lr * scale), -(lr * wd)
+};
+template <bool MUON>
+using MuonOf = std::conditional_t<MUON, MuonItem, NoMuon>;
+
+// One element of an orthogonalised tensor by its arena index: m' from the stage kernel's own
+// function, O from the staging matrix by the orientation's index, the rule's last line; p and
+// buf stored, +0 into g under zero_grad, the EMA; returns the new p.
+template <bool EMA>
+__device__ __forceinline__ float muon_update1(float* __restrict__ p, float* __restrict__ g,
+                                              float* __restrict__ buf, size_t i, const SgdHyper& h,
+                                              const EmaOf<EMA>& m, const MuonItem& z) {
+  float b = buf[i];
+  (void)muon_dir(g[i], b, h.grad_scale, h.momentum, h.nesterov);
+  const unsigned el = (unsigned)(i - (size_t)z.t.p_offset), rest = (unsigned)z.t.rest;
+  const unsigned r = el / rest, c = el - r * rest;
+  const float o = bf2f(z.t.x[z.t.transposed ? (size_t)c * z.t.pitch + r : (size_t)r * z.t.pitch + c]);
+  const float pv = p[i];
+  const float np = __builtin_fmaf(z.nls, o, __builtin_fmaf(z.nlw, pv, pv));
+  p[i] = np;
+  buf[i] = b;
+  if (h.zero_grad) g[i] = 0.f;
+  ema1<EMA>(m, i, np);
+  return np;
 }
 
 // A skipped step's share of a work item of kind 0-3: its gradient range, cleared.
@@ -572,14 +580,15 @@ __device__ __forceinline__ void guard_clear(const int4& it, const ConvDesc* __re
   for (int i = threadIdx.x; i < it.z; i += 256) gp[i] = 0.f;
 }
 
-template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB, bool MUON>
 __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
                                               const ConvDesc* __restrict__ descs,
                                               float* __restrict__ p, float* __restrict__ g,
                                               float* __restrict__ buf, const SgdHyper& h,
                                               float* tile, float trust, const GuardState& gd,
                                               const EmaOf<EMA>& m, float* v,
-                                              const RuleOf<ADAM, LAMB>& r) {
+                                              const RuleOf<ADAM, LAMB>& r,
+                                              const MuonOf<MUON>& mz) {
   const int4 it = items[blockIdx.x];
   const int kind = item_kind(it);
   const int tid = threadIdx.x;
@@ -604,6 +613,17 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
     }
   }
   const int cnt = it.z;  // (elementwise items)
+  if constexpr (MUON) {
+    if (mz.on && kind != 1) {  // kinds 0 and 2, element by element (kind 1: in its own case)
+      const size_t off = elem_offset(it, descs);
+      unsigned short* wc = kind == 2 ? descs[it.w].wc + (unsigned)it.y : nullptr;
+      for (int i = tid; i < cnt; i += 256) {
+        const float np = muon_update1<EMA>(p, g, buf, off + i, h, m, mz);
+        if (wc) wc[i] = f2bf(np);
+      }
+      return;
+    }
+  }
   switch (kind) {
     case 0: {
       const size_t off = elem_offset(it, descs);
@@ -659,9 +679,16 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
       const ConvDesc& d = descs[it.y];
       const Tile t(d, it);
       // 1) SGD on the master for the tile's real channels, new values into the LDS tile
-      t.for_each_master([&](size_t gi, int li) {
-        tile[li] = update1<LARS, EMA, ADAM, LAMB>(p, g, buf, v, gi, h, trust, m, r);
-      });
+      if constexpr (MUON) {
+        t.for_each_master([&](size_t gi, int li) {
+          tile[li] = mz.on ? muon_update1<EMA>(p, g, buf, gi, h, m, mz)
+                           : update1<LARS, EMA, ADAM, LAMB>(p, g, buf, v, gi, h, trust, m, r);
+        });
+      } else {
+        t.for_each_master([&](size_t gi, int li) {
+          tile[li] = update1<LARS, EMA, ADAM, LAMB>(p, g, buf, v, gi, h, trust, m, r);
+        });
+      }
       __syncthreads();
       // 2) Wc[k][r][s][c] (c fastest, zero for padded channels)
       if (d.wc) {
@@ -686,17 +713,18 @@ __device__ __forceinline__ void sgd_pack_body(const int4* __restrict__ items,
 }
 
 // The kernel's arguments behind the tables and arenas (their __restrict__ keeps the table reads
-// scalar): SgdHyper, then LarsArgs, ClipArgs, EmaArgs, AdamArgs and LambArgs only in the
+// scalar): SgdHyper, then LarsArgs, ClipArgs, EmaArgs, AdamArgs, LambArgs and MuonArgs only in the
 // instantiations that read them (an empty base takes no kernarg bytes; an empty struct argument
 // would).
 struct NoLars {};
 struct NoClip {};
 struct NoLamb {};
-template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB = false>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB = false, bool MUON = false>
 struct UpdateArgs : SgdHyper, std::conditional_t<LARS, LarsArgs, NoLars>,
                     std::conditional_t<GUARD, ClipArgs, NoClip>, EmaOf<EMA>,
                     std::conditional_t<ADAM, AdamArgs, NoAdam>,
-                    std::conditional_t<LAMB, LambArgs, NoLamb> {};
+                    std::conditional_t<LAMB, LambArgs, NoLamb>,
+                    std::conditional_t<MUON, MuonArgs, NoMuon> {};
 static_assert(sizeof(UpdateArgs<false, false, false, false>) == 96 &&
               sizeof(UpdateArgs<false, true, false, false>) == 128 &&
               sizeof(UpdateArgs<true, false, false, false>) == 136 &&
@@ -712,8 +740,13 @@ static_assert(sizeof(UpdateArgs<false, false, false, false>) == 96 &&
               sizeof(UpdateArgs<false, false, false, true, true>) == 168 &&
               sizeof(UpdateArgs<false, true, false, true, true>) == 200 &&
               sizeof(UpdateArgs<false, false, true, true, true>) == 184 &&
-              sizeof(UpdateArgs<false, true, true, true, true>) == 216,
-              "kernarg bytes of the sixteen instantiations (ADAM excludes LARS, LAMB needs ADAM)");
+              sizeof(UpdateArgs<false, true, true, true, true>) == 216 &&
+              sizeof(UpdateArgs<false, false, false, false, false, true>) == 112 &&
+              sizeof(UpdateArgs<false, true, false, false, false, true>) == 144 &&
+              sizeof(UpdateArgs<false, false, true, false, false, true>) == 128 &&
+              sizeof(UpdateArgs<false, true, true, false, false, true>) == 160,
+              "kernarg bytes of the twenty instantiations (ADAM excludes LARS, LAMB needs ADAM, "
+              "MUON excludes both)");
 
 // ADAM: this step's {learning rate, a1, a2} (api.h AdamArgs), read once per block where the plain
 // instantiations read the learning rate: thread 0 loads, LDS broadcast, one barrier. The step
@@ -831,14 +864,15 @@ __global__ __launch_bounds__(256) void lamb_norms_kernel(LambNormArgs<GUARD> a) 
   }
 }
 
-template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM, bool LAMB, bool MUON>
 __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ items,
                                                        const ConvDesc* __restrict__ descs,
                                                        float* __restrict__ p,
                                                        float* __restrict__ g,
                                                        float* __restrict__ buf,
-                                                       UpdateArgs<LARS, GUARD, EMA, ADAM, LAMB> a) {
+                                                       UpdateArgs<LARS, GUARD, EMA, ADAM, LAMB, MUON> a) {
   static_assert(!(LARS && ADAM), "AdamW has no trust ratios");
+  static_assert(!(MUON && (LARS || ADAM)), "Muon rides on the plain momentum rule");
   static_assert(ADAM || !LAMB, "LAMB is a rule on AdamW's moments");
   __shared__ float tile[kTileElems];
   SgdHyper h = a;
@@ -867,8 +901,17 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(const int4* __restrict__ 
     rule.nlt = -(h.lr * (none ? 1.f : lamb_trust_block(a)));
   }
   if constexpr (GUARD) h.grad_scale *= gd.c;
-  sgd_pack_body<LARS, GUARD, EMA, ADAM, LAMB>(items, descs, p, g, buf, h, tile, trust, gd, a, v,
-                                              rule);
+  MuonOf<MUON> mz{};
+  if constexpr (MUON) {  // (the kind word: a scalar load, uniform over the block)
+    mz.on = (items[blockIdx.x].x & kItemMuon) != 0;
+    if (mz.on) {
+      mz.t = a.tensors[static_cast<const MuonArgs&>(a).side[blockIdx.x]];
+      mz.nls = -(h.lr * mz.t.scale);
+      mz.nlw = -(h.lr * h.wd);
+    }
+  }
+  sgd_pack_body<LARS, GUARD, EMA, ADAM, LAMB, MUON>(items, descs, p, g, buf, h, tile, trust, gd, a,
+                                                    v, rule, mz);
   if (h.signal && last_block_done(h.done)) signal_flag(h.done, h.signal);
 }
 
@@ -922,9 +965,9 @@ __global__ void counter_add_kernel(int* c, int delta, LrSched* sched, int sched_
   __hip_atomic_store(&sched->step, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool LARS, bool GUARD, bool EMA, bool ADAM = false, bool LAMB = false>
+template <bool LARS, bool GUARD, bool EMA, bool ADAM = false, bool LAMB = false, bool MUON = false>
 static int launch_update(const UpdateLaunch& u, hipStream_t st) {
-  UpdateArgs<LARS, GUARD, EMA, ADAM, LAMB> a{};
+  UpdateArgs<LARS, GUARD, EMA, ADAM, LAMB, MUON> a{};
   static_cast<SgdHyper&>(a) = u.h;
   a.sched_advance = a.sched && a.sched_advance ? 1 : 0;
   if constexpr (LARS) static_cast<LarsArgs&>(a) = u.lars;
@@ -932,8 +975,9 @@ static int launch_update(const UpdateLaunch& u, hipStream_t st) {
   if constexpr (EMA) static_cast<EmaArgs&>(a) = u.ema;
   if constexpr (ADAM) static_cast<AdamArgs&>(a) = u.adam;
   if constexpr (LAMB) static_cast<LambArgs&>(a) = u.lamb;
-  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA, ADAM, LAMB>), dim3(u.n_items), dim3(256), 0,
-                     st, u.items, u.descs, u.p, u.g, u.buf, a);
+  if constexpr (MUON) static_cast<MuonArgs&>(a) = u.muon;
+  hipLaunchKernelGGL((sgd_pack_kernel<LARS, GUARD, EMA, ADAM, LAMB, MUON>), dim3(u.n_items),
+                     dim3(256), 0, st, u.items, u.descs, u.p, u.g, u.buf, a);
   return (int)hipGetLastError();
 }
 
@@ -998,6 +1042,7 @@ extern "C" int ddp_sgd_pack(const UpdateLaunch* u, hipStream_t st) {
   const bool lamb = u->lamb.side;
   if (lamb && (!u->adam.v || lars || !u->lamb.tensors || !u->lamb.partial || !u->lamb.trust))
     return -1;
+  if (u->muon.side && u->adam.v) return -1;
   if (u->adam.v) {  // AdamW: the step number comes from the schedule's step word
     if (lars || !u->adam.bias || !u->adam.n_bias || !u->h.sched) return -1;
     if (lamb) {
@@ -1012,6 +1057,14 @@ extern "C" int ddp_sgd_pack(const UpdateLaunch* u, hipStream_t st) {
                     : launch_update<false, false, true, true>)(*u, st);
     return (guard ? launch_update<false, true, false, true>
                   : launch_update<false, false, false, true>)(*u, st);
+  }
+  if (u->muon.side) {
+    if (lars || !u->muon.tensors) return -1;
+    if (u->ema.ema)
+      return (guard ? launch_update<false, true, true, false, false, true>
+                    : launch_update<false, false, true, false, false, true>)(*u, st);
+    return (guard ? launch_update<false, true, false, false, false, true>
+                  : launch_update<false, false, false, false, false, true>)(*u, st);
   }
   if (u->ema.ema)
     return (lars ? (guard ? launch_update<true, true, true> : launch_update<true, false, true>)

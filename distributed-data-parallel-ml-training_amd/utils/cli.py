@@ -77,7 +77,7 @@ def build_parser(description=None, distributed=True):
     g.add_argument('--min-lr', type=float, default=0.0, help='end value of cosine / linear')
     g.add_argument('--lr-ref-batch', type=int, default=None,
                    help='linear scaling rule: lr *= global batch / this batch')
-    g.add_argument('--optimizer', default='sgd', choices=['sgd', 'lars', 'adamw', 'lamb'],
+    g.add_argument('--optimizer', default='sgd', choices=['sgd', 'lars', 'adamw', 'lamb', 'muon'],
                    help='sgd (reference) | lars: every weight tensor\'s update scaled by its trust '
                         'ratio eta |w| / (|g| + wd |w| + eps), for the learning rates that the '
                         'linear scaling rule gives a large global batch (works inside --graph) | '
@@ -85,12 +85,19 @@ def build_parser(description=None, distributed=True):
                         'update launch (works inside --graph; pass an Adam-sized --lr, 0.001) | '
                         'lamb: the AdamW update with every weight tensor\'s step scaled by its '
                         'trust ratio |w| / |update|, for Adam at a large global batch (one more '
-                        'launch per update; works inside --graph)')
+                        'launch per update; works inside --graph) | muon: the momentum of every '
+                        'conv filter orthogonalised by a Newton-Schulz iteration on MFMA GEMMs, '
+                        'SGD momentum for every other tensor (17 more launches per update; works '
+                        'inside --graph; pass a Muon-sized --lr, 0.02)')
+    g.add_argument('--muon-momentum', type=_adam_beta, default=0.95,
+                   help='--optimizer muon: momentum of every tensor (nesterov), in [0, 1)')
+    g.add_argument('--muon-ns-steps', type=_ns_steps, default=5,
+                   help='--optimizer muon: Newton-Schulz iterations per update')
     g.add_argument('--adam-beta1', type=_adam_beta, default=0.9)
     g.add_argument('--adam-beta2', type=_adam_beta, default=0.999)
     g.add_argument('--adam-eps', type=_non_negative('--adam-eps'), default=1e-8)
     g.add_argument('--weight-decay', type=_non_negative('--weight-decay'), default=None,
-                   help="weight decay; default: the optimizer's own, 1e-4 for sgd and lars "
+                   help="weight decay; default: the optimizer's own, 1e-4 for sgd, lars and muon "
                         "(reference), 1e-2 for adamw and lamb")
     g.add_argument('--lars-eta', type=float, default=0.001, help='LARS trust coefficient')
     g.add_argument('--lars-eps', type=float, default=1e-8)
@@ -130,6 +137,13 @@ def _num_classes(v):
     n = int(v)
     if n < 2:
         raise argparse.ArgumentTypeError("--num-classes must be >= 2")
+    return n
+
+
+def _ns_steps(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError("--muon-ns-steps must be >= 1")
     return n
 
 
@@ -181,11 +195,13 @@ def optimizer_from_args(args, params, lr):
     """The run's optimizer: the reference's SGD(lr, 0.9, 1e-4), or LARS over the same
     hyper-parameters with --optimizer lars (biases and BatchNorm vectors are not adapted), or
     AdamW(lr, (--adam-beta1, --adam-beta2), --adam-eps, 1e-2) with --optimizer adamw, or LAMB over
-    AdamW's hyper-parameters with --optimizer lamb (biases and BatchNorm vectors are not adapted);
+    AdamW's hyper-parameters with --optimizer lamb (biases and BatchNorm vectors are not adapted),
+    or Muon(lr, --muon-momentum, nesterov, --muon-ns-steps) with --optimizer muon (every 4-D
+    parameter is orthogonalised, the others take the momentum rule);
     --weight-decay replaces the optimizer's default decay; --clip-grad-norm /
     --skip-nonfinite-grads switch the gradient guard of any of them on; --no-decay-1d takes the
     decay off biases and BatchNorm vectors in any of them."""
-    from ..optim import FusedSGD, LAMB, LARS, AdamW
+    from ..optim import FusedSGD, LAMB, LARS, AdamW, Muon
     guard = {}
     if getattr(args, "clip_grad_norm", None) is not None or \
             getattr(args, "skip_nonfinite_grads", False):
@@ -201,6 +217,9 @@ def optimizer_from_args(args, params, lr):
                    eps=getattr(args, "adam_eps", 1e-8),
                    weight_decay=0.01 if wd is None else wd, **guard)
     wd = 0.0001 if wd is None else wd
+    if getattr(args, "optimizer", "sgd") == "muon":
+        return Muon(params, lr=lr, momentum=getattr(args, "muon_momentum", 0.95), nesterov=True,
+                    weight_decay=wd, ns_steps=getattr(args, "muon_ns_steps", 5), **guard)
     if getattr(args, "optimizer", "sgd") == "lars":
         return LARS(params, lr=lr, momentum=0.9, weight_decay=wd,
                     trust_coefficient=args.lars_eta, eps=args.lars_eps, **guard)
