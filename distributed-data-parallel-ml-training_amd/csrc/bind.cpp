@@ -185,6 +185,35 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("g"), py::arg("x"), py::arg("wc"), py::arg("bias"), py::arg("z"), py::arg("stats"),
      py::arg("ws"), py::arg("ws_elems"), py::arg("st"), py::arg("bn") = py::none(),
      py::arg("fin") = py::none());
+  // grouped 3x3 convolution (conv_group.hip; api.h ddp_gconv_*): gconv_ok = the geometry is
+  // served; the launchers raise unless it is
+  m.def("gconv_ok", [](py::tuple g, int groups) {
+    auto c = geom(g);
+    return ddp_gconv_ok(&c, groups) != 0;
+  });
+  auto gconv_check = [](int rc, const char* what) {
+    if (rc < 0) throw std::runtime_error(std::string(what) + ": geometry not served or invalid "
+                                         "arguments (" + std::to_string(rc) + ")");
+    if (rc >= 2) check(rc - 2, what);
+  };
+  m.def("gconv_fwd", [gconv_check](py::tuple g, int groups, uintptr_t x, uintptr_t wc,
+                                   uintptr_t bias, uintptr_t z, uintptr_t stats, uintptr_t st) {
+    auto c = geom(g);
+    gconv_check(ddp_gconv_fwd(&c, groups, P<void>(x), P<void>(wc), P<float>(bias), P<void>(z),
+                              P<float>(stats), S(st)), "gconv_fwd");
+  });
+  m.def("gconv_dgrad", [gconv_check](py::tuple g, int groups, uintptr_t dz, uintptr_t wc,
+                                     uintptr_t dx, uintptr_t st) {
+    auto c = geom(g);
+    gconv_check(ddp_gconv_dgrad(&c, groups, P<void>(dz), P<void>(wc), P<void>(dx), S(st)),
+                "gconv_dgrad");
+  });
+  m.def("gconv_wgrad", [gconv_check](py::tuple g, int groups, uintptr_t dz, uintptr_t x,
+                                     uintptr_t dw, uintptr_t ws, size_t ws_elems, uintptr_t st) {
+    auto c = geom(g);
+    gconv_check(ddp_gconv_wgrad(&c, groups, P<void>(dz), P<void>(x), P<float>(dw), P<float>(ws),
+                                ws_elems, S(st)), "gconv_wgrad");
+  });
   // VGG input block with z recomputed (conv_l0.hip): forward = statistics + BN/ReLU/pool
   // passes into y; backward = BN-backward sums + dz passes (dgamma / dbeta accumulated)
   m.def("l0_ok", [](py::tuple g) {

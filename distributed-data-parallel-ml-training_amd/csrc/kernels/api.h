@@ -496,6 +496,24 @@ int ddp_conv_tr_would_serve(const ddp_amd::ConvGeom* g, size_t ws_elems, int in_
 // (bm, bn, splits, stages) (bm = 0: use the implicit-GEMM kernel), 3 force the same (sweeps)
 void ddp_conv_tr_set(int mode, int M, int K, int C, int H, int bm, int bn, int splits, int stages);
 int ddp_conv_tr_geometry(int BM, int N, int H, int W, int* out7);
+// grouped 3x3 convolution (conv_group.hip): R = S = 3, pad 1, dilation 1, stride 1 or 2, C == K,
+// C % 32 == 0, Cg = C / groups in {4, 8, 16, 32}, any N, H, W >= 1 (a one-row band of the image
+// must fit LDS: W <= 800). ``g`` is the layer's ConvGeom with C = K = the activation's channel
+// count and Creal = Cg; x, dz, z, dx are bf16 NHWC over all channels, wc is the bf16 operand copy
+// [K][3][3][pad8(Cg)] (pad channels are not read), the fp32 gradient is [K][Cg][3][3] or
+// [K][3][3][Cg] (ConvGeom::wkrsc). ok: 1 = this geometry is served, 0 = not. The launchers
+// return 1 when served, < 0 for invalid arguments (-1: geometry not served or a null pointer,
+// -2: workspace below C / 32 * 9216 floats), >= 2 HIP error (rc - 2).
+// fwd: z = conv(x) + bias, stats as ddp_conv_fwd (bias and stats may be null); dgrad: dx written
+// whole; wgrad: dw += the gradient, through fp32 partials in ``ws`` added in a fixed order (no
+// float atomics, no optimizer step)
+int ddp_gconv_ok(const ddp_amd::ConvGeom* g, int groups);
+int ddp_gconv_fwd(const ddp_amd::ConvGeom* g, int groups, const void* x, const void* wc,
+                  const float* bias, void* z, float* stats, hipStream_t st);
+int ddp_gconv_dgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, const void* wc,
+                    void* dx, hipStream_t st);
+int ddp_gconv_wgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, const void* x,
+                    float* dw, float* ws, size_t ws_elems, hipStream_t st);
 // classifier-head dx fused with the preceding block's whole BN backward + dW / db in one launch
 // (conv_igemm.hip linear_head_bwd_kernel): 1 launched, 0 not served, < 0 invalid, >= 2 HIP
 // error (rc - 2)

@@ -1,4 +1,5 @@
-"""Model zoo: VGG-11/13/16/19 (reference family) and ResNet-50 (driver's large-gradient config)."""
+"""Model zoo: VGG-11/13/16/19 (reference family) ResNet-50 (driver's large-gradient config) and
+ResNeXt-50 32x4d (the same module tree with a grouped conv2)."""
 from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG  # noqa: F401
 
 
@@ -12,4 +13,9 @@ def build(name, num_classes=None):
     if name in ("resnet50", "resnet-50"):
         from .resnet import resnet50
         return resnet50(**kw)
+    # "resnet50_32x4d" is an alias: bench.py and engine/step.py default_cuts recognise the ResNet
+    # family by startswith("resnet"), so that spelling runs ResNeXt-50 through both unchanged
+    if name in ("resnext50_32x4d", "resnet50_32x4d"):
+        from .resnet import resnext50_32x4d
+        return resnext50_32x4d(**kw)
     raise ValueError(f"unknown model {name}")

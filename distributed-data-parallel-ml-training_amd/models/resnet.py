@@ -23,13 +23,17 @@ STEM_POOL_FUSE = True
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * self.expansion, 1, bias=False)
+        # ResNeXt (torchvision's rule): conv2 is grouped over a wider bottleneck; its GPU path
+        # is the grouped 3x3 kernel (csrc/kernels/conv_group.hip)
+        width = int(planes * base_width / 64) * groups
+        self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups,
+                               bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, planes * self.expansion, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -79,9 +83,11 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, zero_init_residual=False):
+    def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, zero_init_residual=False,
+                 groups=1, width_per_group=64):
         super().__init__()
         self.inplanes = 64
+        self.groups, self.base_width = groups, width_per_group
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -111,10 +117,11 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(
                 nn.Conv2d(self.inplanes, planes * Bottleneck.expansion, 1, stride=stride, bias=False),
                 nn.BatchNorm2d(planes * Bottleneck.expansion))
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample)]
+        kw = dict(groups=self.groups, base_width=self.base_width)
+        layers = [Bottleneck(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * Bottleneck.expansion
         for _ in range(1, blocks):
-            layers.append(Bottleneck(self.inplanes, planes))
+            layers.append(Bottleneck(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def blocks(self):
@@ -218,3 +225,8 @@ class ResNet(nn.Module):
 
 def resnet50(num_classes=1000):
     return ResNet((3, 4, 6, 3), num_classes)
+
+
+def resnext50_32x4d(num_classes=1000):
+    """ResNeXt-50 32x4d (torchvision's keys and shapes): 25 028 904 parameters."""
+    return ResNet((3, 4, 6, 3), num_classes, groups=32, width_per_group=4)

@@ -31,8 +31,8 @@ class ConvBNActSpec:
 
     def __init__(self, conv, bn, relu=True, pool=False, cin_pad=None, residual=False):
         K, Cr, R, S = conv.weight.shape
-        if conv.groups != 1 or conv.dilation != (1, 1):
-            raise ValueError("grouped/dilated conv not supported")
+        if conv.dilation != (1, 1):
+            raise ValueError("dilated conv not supported")
         if conv.stride[0] != conv.stride[1] or conv.padding[0] != conv.padding[1]:
             raise ValueError("only square stride/padding supported")
         if K % 8:
@@ -40,14 +40,27 @@ class ConvBNActSpec:
         self.conv, self.bn = conv, bn
         self.K, self.Cr, self.R, self.S = K, Cr, R, S
         self.C = cin_pad if cin_pad is not None else _pad8(Cr)
+        # operand pitch: channels per filter tap of the bf16 copy Wc
+        self.Cp = self.C
         self.stride, self.pad = conv.stride[0], conv.padding[0]
+        # grouped conv (conv_group.hip): C stays the activation's channel count, Cr and the
+        # operand pitch are the group's (Cg, pad8(Cg)). No other kernel takes it.
+        self.groups = conv.groups
+        if self.groups > 1:
+            self.C, self.Cp = conv.in_channels, _pad8(Cr)
+            if cin_pad is not None or not native().gconv_ok(self.geom(1, 8, 8), self.groups):
+                raise ValueError(
+                    "grouped conv is served for 3x3 kernels with padding 1, stride 1 or 2, equal "
+                    "input and output channels that are a multiple of 32, and 4, 8, 16 or 32 "
+                    f"channels per group (got {conv.in_channels} -> {K} channels, {R}x{S}, "
+                    f"stride {self.stride}, padding {self.pad}, {Cr} per group)")
         self.relu, self.pool, self.residual = relu, pool, residual
         # ResNet stem: BatchNorm + ReLU + MaxPool2d(3, 2, 1) fused (bn_act.hip bn_pool3_*; the
         # pre-pool activation and its gradient are never materialised). Set by models/resnet.py
         self.maxpool3 = False
         self.eps = float(bn.eps) if bn is not None else 1e-5
         dev = conv.weight.device
-        self.wc = torch.empty(K, R, S, self.C, dtype=BF16, device=dev)
+        self.wc = torch.empty(K, R, S, self.Cp, dtype=BF16, device=dev)
         # transposed copy [C][R][S][K]: none. The backward-data GEMM reads Wc k-major through
         # transposing LDS reads (ds_read_b64_tr_b16); the optimizer's repack keeps the slot
         self.wt = None
@@ -84,7 +97,7 @@ class ConvBNActSpec:
 
     def pack_desc(self):
         w = self.conv.weight
-        return (ptr(w), ptr(self.wc), ptr(self.wt), self.K, self.Cr, self.C,
+        return (ptr(w), ptr(self.wc), ptr(self.wt), self.K, self.Cr, self.Cp,
                 self.R, self.S, weight_krsc(w))
 
     def rebind_wc(self, flat):
@@ -150,6 +163,14 @@ def conv_forward(spec, x, bias=None, stats=None, bn_fuse=None, fin=None):
     g = spec.geom(N, H, W)
     P, Q = g[9], g[10]
     z = torch.empty(N, P, Q, spec.K, dtype=BF16, device=x.device)
+    if spec.groups > 1:
+        # grouped 3x3 (conv_group.hip): no BatchNorm-forward fusion and no fused input; a
+        # geometry outside its range is an error, not a fallback
+        if fin is not None:
+            _bn_act_fwd_now(fin, fin.fwd_z, x)
+        native().gconv_fwd(g, spec.groups, ptr(x), ptr(spec.wc), ptr(bias), ptr(z), ptr(stats),
+                           stream_handle())
+        return (z, False) if bn_fuse is not None else z
     if spec.C == 8 and native().conv_fwd_smallk(g, ptr(x), ptr(spec.wc), ptr(bias), ptr(z),
                                                 ptr(stats), stream_handle()):
         # input layer (3 channels padded to 8): direct MFMA kernel, conv_smallk.hip
@@ -312,6 +333,19 @@ def conv_backward(spec, x, dz, dweight, need_dx, link=None, weight=None, bnf=Non
     g = spec.geom(N, H, W, weight_krsc(dweight))
     s = stream_handle()
     ws = workspace(x.device)
+    if spec.groups > 1:
+        # grouped 3x3 (conv_group.hip): its own WGRAD (partials + a fixed-order finish that takes
+        # no optimizer step) and DGRAD; it offers the preceding block no BatchNorm-backward work
+        if link is not None:
+            raise RuntimeError("a grouped conv cannot be the first conv of a residual branch")
+        native().gconv_wgrad(g, spec.groups, ptr(dz), ptr(x), ptr(dweight), ptr(ws), ws.numel(), s)
+        if weight is not None:
+            grad_ready([weight])
+        dx = None
+        if need_dx:
+            dx = torch.empty_like(x)
+            native().gconv_dgrad(g, spec.groups, ptr(dz), ptr(spec.wc), ptr(dx), s)
+        return (dx, False) if (bna is not None or (bnf is not None and len(bnf) > 7)) else dx
     if need_dx and link is None and spec.stride == 1 and spec.C == spec.Cr:
         # wgrad + dgrad of this layer as one grouped launch (+ one finish launch) when the
         # kernel policy allows it (conv_igemm.hip ddp_conv_bwd_pair), else the two launches
@@ -682,6 +716,7 @@ class _ConvBNActFn(torch.autograd.Function):
         prev = spec.prev
         if (_common.BN_BWD_FUSE and prev is not None and ctx.prev_z is not None
                 and ctx.needs_input_grad[0] and ctx.in_link is None and spec.stride == 1
+                and spec.groups == 1  # (a grouped DGRAD takes no BatchNorm-backward work)
                 and not prev.residual and prev.K == spec.C and spec.C == spec.Cr
                 and bn_bwd_fuse_pays(x.shape[1], x.shape[2], prev.pool, x.shape[0])):
             pz = ctx.prev_z
@@ -695,7 +730,7 @@ class _ConvBNActFn(torch.autograd.Function):
         if (bnf is None and L0_SUMS_IN_FINISH and l0c is not None and ctx.needs_input_grad[0]
                 and x.shape[0] <= L0_SUMS_IN_FINISH_MAX_BATCH
                 and ctx.in_link is None and spec.stride == 1 and prev.K == spec.C
-                and spec.C == spec.Cr and x.shape[1] * 2 == prev._out_p):
+                and spec.groups == 1 and spec.C == spec.Cr and x.shape[1] * 2 == prev._out_p):
             # the input block's BN-backward sums in this dgrad's split-K finish (conv_l0.hip's
             # recorded window codes + winner z): its backward skips l0_sums_kernel
             code, zw = l0c
@@ -966,6 +1001,7 @@ class LinearGemmSpec(ConvBNActSpec):
         self.linear = linear
         self.conv, self.bn = linear, None
         self.K, self.Cr, self.R, self.S, self.C = J, F, 1, 1, F
+        self.Cp, self.groups = F, 1
         self.stride, self.pad = 1, 0
         self.relu, self.pool, self.residual = False, False, False
         self.eps = 1e-5

@@ -705,6 +705,8 @@ class FusedSGD(torch.optim.SGD):
             pp, wc, wt, K, Cr, C, R, S, krsc = p._ddp_amd_pack()
             if wt or not wc or not (krsc or R * S == 1) or pp != base_p + 4 * a.offsets[i]:
                 continue
+            if getattr(p._ddp_amd_pack.__self__, "groups", 1) > 1:
+                continue  # grouped conv (conv_group.hip): its WGRAD finish takes no step
             dw = base_g + 4 * a.offsets[i]
             nat.sgd_fuse_register(dw, pp, base_b + 4 * a.offsets[i], wc, float(g["lr"]),
                                   float(g["momentum"]), self._wd_of(i),
