@@ -214,6 +214,29 @@ PYBIND11_MODULE(_native, m) {
     gconv_check(ddp_gconv_wgrad(&c, groups, P<void>(dz), P<void>(x), P<float>(dw), P<float>(ws),
                                 ws_elems, S(st)), "gconv_wgrad");
   });
+  // depthwise 3x3 convolution (dwconv.hip; api.h ddp_dwconv_*), bound as the grouped one
+  m.def("dwconv_ok", [](py::tuple g, int groups) {
+    auto c = geom(g);
+    return ddp_dwconv_ok(&c, groups) != 0;
+  });
+  m.def("dwconv_fwd", [gconv_check](py::tuple g, int groups, uintptr_t x, uintptr_t wc,
+                                    uintptr_t bias, uintptr_t z, uintptr_t stats, uintptr_t st) {
+    auto c = geom(g);
+    gconv_check(ddp_dwconv_fwd(&c, groups, P<void>(x), P<void>(wc), P<float>(bias), P<void>(z),
+                               P<float>(stats), S(st)), "dwconv_fwd");
+  });
+  m.def("dwconv_dgrad", [gconv_check](py::tuple g, int groups, uintptr_t dz, uintptr_t wc,
+                                      uintptr_t dx, uintptr_t st) {
+    auto c = geom(g);
+    gconv_check(ddp_dwconv_dgrad(&c, groups, P<void>(dz), P<void>(wc), P<void>(dx), S(st)),
+                "dwconv_dgrad");
+  });
+  m.def("dwconv_wgrad", [gconv_check](py::tuple g, int groups, uintptr_t dz, uintptr_t x,
+                                      uintptr_t dw, uintptr_t ws, size_t ws_elems, uintptr_t st) {
+    auto c = geom(g);
+    gconv_check(ddp_dwconv_wgrad(&c, groups, P<void>(dz), P<void>(x), P<float>(dw), P<float>(ws),
+                                 ws_elems, S(st)), "dwconv_wgrad");
+  });
   // VGG input block with z recomputed (conv_l0.hip): forward = statistics + BN/ReLU/pool
   // passes into y; backward = BN-backward sums + dz passes (dgamma / dbeta accumulated)
   m.def("l0_ok", [](py::tuple g) {

@@ -514,6 +514,21 @@ int ddp_gconv_dgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, cons
                     void* dx, hipStream_t st);
 int ddp_gconv_wgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, const void* x,
                     float* dw, float* ws, size_t ws_elems, hipStream_t st);
+// depthwise 3x3 convolution (dwconv.hip): R = S = 3, pad 1, dilation 1, stride 1 or 2,
+// C == K == groups (one channel per group, Creal = 1), C % 8 == 0, any N, H, W >= 1, tensors
+// below 2^31 elements. x, dz, z, dx are bf16 NHWC, wc is the bf16 operand copy [K][3][3][8]
+// (elements 1..7 of each pitch are not read), the fp32 gradient is [K][1][3][3] or [K][3][3][1]
+// (the same element order). Return codes as ddp_gconv_* (-2: workspace below 9 C floats).
+// fwd: z = conv(x) + bias, stats as ddp_conv_fwd (bias and stats may be null); dgrad: dx written
+// whole; wgrad: dw += the gradient, through fp32 partials in ``ws`` added in a fixed order (no
+// float atomics, no optimizer step)
+int ddp_dwconv_ok(const ddp_amd::ConvGeom* g, int groups);
+int ddp_dwconv_fwd(const ddp_amd::ConvGeom* g, int groups, const void* x, const void* wc,
+                   const float* bias, void* z, float* stats, hipStream_t st);
+int ddp_dwconv_dgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, const void* wc,
+                     void* dx, hipStream_t st);
+int ddp_dwconv_wgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, const void* x,
+                     float* dw, float* ws, size_t ws_elems, hipStream_t st);
 // classifier-head dx fused with the preceding block's whole BN backward + dW / db in one launch
 // (conv_igemm.hip linear_head_bwd_kernel): 1 launched, 0 not served, < 0 invalid, >= 2 HIP
 // error (rc - 2)

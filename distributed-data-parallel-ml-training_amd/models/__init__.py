@@ -1,5 +1,6 @@
-"""Model zoo: VGG-11/13/16/19 (reference family) ResNet-50 (driver's large-gradient config) and
-ResNeXt-50 32x4d (the same module tree with a grouped conv2)."""
+"""Model zoo: VGG-11/13/16/19 (reference family) ResNet-50 (driver's large-gradient config),
+ResNeXt-50 32x4d (the same module tree with a grouped conv2) and MobileNet v1 (depthwise-separable
+blocks)."""
 from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG  # noqa: F401
 
 
@@ -18,4 +19,7 @@ def build(name, num_classes=None):
     if name in ("resnext50_32x4d", "resnet50_32x4d"):
         from .resnet import resnext50_32x4d
         return resnext50_32x4d(**kw)
+    if name in ("mobilenet_v1", "mobilenet"):
+        from .mobilenet import mobilenet_v1
+        return mobilenet_v1(**kw)
     raise ValueError(f"unknown model {name}")

@@ -46,13 +46,18 @@ class ConvBNActSpec:
         # grouped conv (conv_group.hip): C stays the activation's channel count, Cr and the
         # operand pitch are the group's (Cg, pad8(Cg)). No other kernel takes it.
         self.groups = conv.groups
+        # depthwise conv (dwconv.hip): one channel per group; the operand copy keeps the pitch 8
+        self.depthwise = False
         if self.groups > 1:
             self.C, self.Cp = conv.in_channels, _pad8(Cr)
-            if cin_pad is not None or not native().gconv_ok(self.geom(1, 8, 8), self.groups):
+            self.depthwise = self.groups == conv.in_channels == K and Cr == 1
+            ok = native().dwconv_ok if self.depthwise else native().gconv_ok
+            if cin_pad is not None or not ok(self.geom(1, 8, 8), self.groups):
                 raise ValueError(
                     "grouped conv is served for 3x3 kernels with padding 1, stride 1 or 2, equal "
                     "input and output channels that are a multiple of 32, and 4, 8, 16 or 32 "
-                    f"channels per group (got {conv.in_channels} -> {K} channels, {R}x{S}, "
+                    "channels per group, or depthwise (one channel per group) with a multiple of "
+                    f"8 channels (got {conv.in_channels} -> {K} channels, {R}x{S}, "
                     f"stride {self.stride}, padding {self.pad}, {Cr} per group)")
         self.relu, self.pool, self.residual = relu, pool, residual
         # ResNet stem: BatchNorm + ReLU + MaxPool2d(3, 2, 1) fused (bn_act.hip bn_pool3_*; the
@@ -168,8 +173,9 @@ def conv_forward(spec, x, bias=None, stats=None, bn_fuse=None, fin=None):
         # geometry outside its range is an error, not a fallback
         if fin is not None:
             _bn_act_fwd_now(fin, fin.fwd_z, x)
-        native().gconv_fwd(g, spec.groups, ptr(x), ptr(spec.wc), ptr(bias), ptr(z), ptr(stats),
-                           stream_handle())
+        # depthwise (dwconv.hip) under the same contract
+        fwd = native().dwconv_fwd if spec.depthwise else native().gconv_fwd
+        fwd(g, spec.groups, ptr(x), ptr(spec.wc), ptr(bias), ptr(z), ptr(stats), stream_handle())
         return (z, False) if bn_fuse is not None else z
     if spec.C == 8 and native().conv_fwd_smallk(g, ptr(x), ptr(spec.wc), ptr(bias), ptr(z),
                                                 ptr(stats), stream_handle()):
@@ -338,13 +344,16 @@ def conv_backward(spec, x, dz, dweight, need_dx, link=None, weight=None, bnf=Non
         # no optimizer step) and DGRAD; it offers the preceding block no BatchNorm-backward work
         if link is not None:
             raise RuntimeError("a grouped conv cannot be the first conv of a residual branch")
-        native().gconv_wgrad(g, spec.groups, ptr(dz), ptr(x), ptr(dweight), ptr(ws), ws.numel(), s)
+        nat = native()
+        wgrad, dgrad = ((nat.dwconv_wgrad, nat.dwconv_dgrad) if spec.depthwise
+                        else (nat.gconv_wgrad, nat.gconv_dgrad))
+        wgrad(g, spec.groups, ptr(dz), ptr(x), ptr(dweight), ptr(ws), ws.numel(), s)
         if weight is not None:
             grad_ready([weight])
         dx = None
         if need_dx:
             dx = torch.empty_like(x)
-            native().gconv_dgrad(g, spec.groups, ptr(dz), ptr(spec.wc), ptr(dx), s)
+            dgrad(g, spec.groups, ptr(dz), ptr(spec.wc), ptr(dx), s)
         return (dx, False) if (bna is not None or (bnf is not None and len(bnf) > 7)) else dx
     if need_dx and link is None and spec.stride == 1 and spec.C == spec.Cr:
         # wgrad + dgrad of this layer as one grouped launch (+ one finish launch) when the

@@ -750,7 +750,9 @@ class FusedSGD(torch.optim.SGD):
                 if not hasattr(p, "_ddp_amd_pack"):
                     continue
                 pp, wc, wt, K, Cr, C, R, S, krsc = p._ddp_amd_pack()
-                if pp != a.data.data_ptr() + 4 * a.offsets[i] or (R * S > 1 and bool(krsc) != a.krsc[i]):
+                # (one input channel, a depthwise weight: both layouts are the same element order)
+                if pp != a.data.data_ptr() + 4 * a.offsets[i] or (
+                        R * S > 1 and Cr > 1 and bool(krsc) != a.krsc[i]):
                     raise RuntimeError("packed conv weight is not a view into the parameter arena")
                 d = len(descs)
                 descs.append([a.offsets[i], K, Cr, C, R, S, wc, wt, int(krsc), 0, 0, 0])
