@@ -237,6 +237,34 @@ PYBIND11_MODULE(_native, m) {
     gconv_check(ddp_dwconv_wgrad(&c, groups, P<void>(dz), P<void>(x), P<float>(dw), P<float>(ws),
                                  ws_elems, S(st)), "dwconv_wgrad");
   });
+  // GroupNorm + ReLU (+ pool) on a resident tile (group_norm.hip; api.h ddp_gn_*): outside
+  // gn_ok the launchers raise "invalid arguments" and write nothing
+  m.def("gn_ok", [](int N, int H, int W, int C, int groups, int pool) {
+    return ddp_gn_ok(N, H, W, C, groups, pool) != 0;
+  });
+  m.def("gn_act_fwd", [](int N, int H, int W, int C, int groups, int pool, int relu, float eps,
+                         uintptr_t z, uintptr_t gamma, uintptr_t beta, uintptr_t y,
+                         uintptr_t table, uintptr_t st) {
+    ddp_amd::GnArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.C = C; a.groups = groups; a.pool = pool; a.relu = relu;
+    a.eps = eps;
+    a.z = P<unsigned short>(z); a.gamma = P<float>(gamma); a.beta = P<float>(beta);
+    a.y = P<unsigned short>(y); a.table = P<float>(table);
+    check(ddp_gn_act_fwd(&a, S(st)), "gn_act_fwd");
+  });
+  m.def("gn_act_bwd", [](int N, int H, int W, int C, int groups, int pool, int relu, float eps,
+                         uintptr_t z, uintptr_t gamma, uintptr_t beta, uintptr_t table,
+                         uintptr_t dy, uintptr_t dz, uintptr_t dgamma, uintptr_t dbeta,
+                         uintptr_t dbias, uintptr_t ws, size_t ws_elems, uintptr_t st) {
+    ddp_amd::GnArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.C = C; a.groups = groups; a.pool = pool; a.relu = relu;
+    a.eps = eps;
+    a.z = P<unsigned short>(z); a.gamma = P<float>(gamma); a.beta = P<float>(beta);
+    a.table = P<float>(table); a.dy = P<unsigned short>(dy); a.dz = P<unsigned short>(dz);
+    a.dgamma = P<float>(dgamma); a.dbeta = P<float>(dbeta); a.dbias = P<float>(dbias);
+    a.ws = P<float>(ws); a.ws_elems = ws_elems;
+    check(ddp_gn_act_bwd(&a, S(st)), "gn_act_bwd");
+  });
   // VGG input block with z recomputed (conv_l0.hip): forward = statistics + BN/ReLU/pool
   // passes into y; backward = BN-backward sums + dz passes (dgamma / dbeta accumulated)
   m.def("l0_ok", [](py::tuple g) {

@@ -72,6 +72,28 @@ struct BnArgs {
   int red_gb;                   // backward reduce launch: channel groups per block (0 = min(C/8, 256))
 };
 
+// GroupNorm + ReLU (+ 2x2 max-pool) on a resident tile (group_norm.hip). No running statistics:
+// eval runs the same forward.
+struct GnArgs {
+  int N, P, Q, C;               // z / pre-pool shape
+  int groups;                   // Cg = C / groups channels share (mu, is) per image
+  int pool;                     // 0: none, 1: 2x2 stride-2 max-pool
+  int relu;                     // apply ReLU
+  float eps;
+  const unsigned short* z;      // conv output (bf16)
+  const float* gamma;           // [C]
+  const float* beta;            // [C]
+  unsigned short* y;            // forward output (bf16, pooled shape)
+  float* table;                 // [N][groups][2] (mu, is): the forward writes, the backward reads
+  const unsigned short* dy;     // backward: grad wrt the block output (pooled shape)
+  unsigned short* dz;           // backward: grad wrt the conv output
+  float* dgamma;                // grad arena slices (accumulated)
+  float* dbeta;
+  float* dbias;                 // the producing conv's bias grad = sum dz (optional)
+  float* ws;                    // backward: fp32 partials [N][3][C]
+  size_t ws_elems;
+};
+
 // BatchNorm-backward statistics fused into a conv dgrad: the dgrad output IS the gradient at the
 // output of the preceding Conv->BN->ReLU(->2x2 max-pool) block, so its epilogue can accumulate
 // that block's backward sums S1 = sum dy_bn, S2 = sum dy_bn * xhat (recomputing the ReLU mask /
@@ -529,6 +551,15 @@ int ddp_dwconv_dgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, con
                      void* dx, hipStream_t st);
 int ddp_dwconv_wgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, const void* x,
                      float* dw, float* ws, size_t ws_elems, hipStream_t st);
+// GroupNorm + ReLU (+ pool) (group_norm.hip). Served (ddp_gn_ok = 1): C % 8 == 0, C % groups
+// == 0, Cg = C / groups a power of two in 1..64, even P and Q with the pool, and
+// max(8, Cg) * P * Q <= 8192 (the tile a workgroup keeps in registers). 0 = launched; -1 = not
+// served or a null pointer, -2 = workspace below N * 3 * C floats (nothing is written); > 0 = HIP
+// error. bwd: dz written whole; dgamma / dbeta / dbias (null: skipped) += through the partials in
+// ``ws`` added in a fixed order (no float atomics)
+int ddp_gn_ok(int N, int P, int Q, int C, int groups, int pool);
+int ddp_gn_act_fwd(const ddp_amd::GnArgs* a, hipStream_t st);
+int ddp_gn_act_bwd(const ddp_amd::GnArgs* a, hipStream_t st);
 // classifier-head dx fused with the preceding block's whole BN backward + dW / db in one launch
 // (conv_igemm.hip linear_head_bwd_kernel): 1 launched, 0 not served, < 0 invalid, >= 2 HIP
 // error (rc - 2)

@@ -4,11 +4,19 @@ blocks)."""
 from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG  # noqa: F401
 
 
-def build(name, num_classes=None):
-    """``num_classes``: the head's output count; None = the model's default."""
+def build(name, num_classes=None, norm="batch", gn_groups=32):
+    """``num_classes``: the head's output count; None = the model's default. ``norm``: "batch"
+    (BatchNorm over the local batch) or "group" (GroupNorm with ``gn_groups`` groups: per-image
+    statistics; the VGG family)."""
     name = name.lower()
     kw = {} if num_classes is None else {"num_classes": int(num_classes)}
     table = {"vgg11": VGG11, "vgg13": VGG13, "vgg16": VGG16, "vgg19": VGG19}
+    if norm not in ("batch", "group"):
+        raise ValueError(f"unknown norm {norm}")
+    if norm == "group":
+        if name not in table:
+            raise ValueError("--norm group is served for vgg11/13/16/19")
+        return table[name](norm="group", gn_groups=int(gn_groups), **kw)
     if name in table:
         return table[name](**kw)
     if name in ("resnet50", "resnet-50"):

@@ -28,8 +28,10 @@ _cfg = {
 IN_CHANNELS_PADDED = 8  # first conv consumes 3 real + 5 zero channels on the MFMA path
 
 
-def _make_layers(cfg):
-    """Same module sequence (and therefore the same Sequential indices) as part1/model.py:11-27."""
+def _make_layers(cfg, norm="batch", gn_groups=32):
+    """Same module sequence (and therefore the same Sequential indices) as part1/model.py:11-27.
+    ``norm="group"``: nn.GroupNorm(gn_groups, v) where the BatchNorm sits (the same parameter
+    names and shapes)."""
     mods = []
     cin = 3
     for v in cfg:
@@ -37,7 +39,8 @@ def _make_layers(cfg):
             mods.append(nn.MaxPool2d(kernel_size=2, stride=2))
             continue
         mods += [nn.Conv2d(cin, v, kernel_size=3, stride=1, padding=1, bias=True),
-                 nn.BatchNorm2d(v, track_running_stats=False),
+                 (nn.GroupNorm(gn_groups, v) if norm == "group"
+                  else nn.BatchNorm2d(v, track_running_stats=False)),
                  nn.ReLU(inplace=True)]
         cin = v
     return nn.Sequential(*mods)
@@ -46,17 +49,20 @@ def _make_layers(cfg):
 class _VGG(nn.Module):
     """VGG module for 3x32x32 input, ``num_classes`` classes (default 10)."""
 
-    def __init__(self, name, num_classes=10):
+    def __init__(self, name, num_classes=10, norm="batch", gn_groups=32):
         super().__init__()
+        if norm not in ("batch", "group"):
+            raise ValueError(f"unknown norm {norm}")
         self.name = name
-        self.layers = _make_layers(_cfg[name])
+        self.norm = norm
+        self.layers = _make_layers(_cfg[name], norm, gn_groups)
         self.fc1 = nn.Linear(512, num_classes)
         self._plan = None
 
     # ------------------------------------------------------------ fused GPU plan
     def fused_plan(self):
         """Group the Sequential into ConvBNAct stages (built once per device)."""
-        from ..ops.layers import ConvBNActSpec
+        from ..ops.layers import ConvBNActSpec, ConvGNActSpec
         dev = self.fc1.weight.device
         if self._plan is not None and self._plan[0] == dev:
             return self._plan[1]
@@ -67,8 +73,16 @@ class _VGG(nn.Module):
             if not isinstance(conv, nn.Conv2d):
                 raise RuntimeError(f"unexpected module {conv} at layers.{i}")
             bn, relu = mods[i + 1], mods[i + 2]
-            assert isinstance(bn, nn.BatchNorm2d) and isinstance(relu, nn.ReLU)
+            assert isinstance(bn, (nn.BatchNorm2d, nn.GroupNorm)) and isinstance(relu, nn.ReLU)
             pool = i + 3 < len(mods) and isinstance(mods[i + 3], nn.MaxPool2d)
+            if isinstance(bn, nn.GroupNorm):
+                # never chained: a GroupNorm block takes none of the BatchNorm fusions
+                hw = 32 >> sum(isinstance(m, nn.MaxPool2d) for m in mods[:i])
+                stages.append(ConvGNActSpec(conv, bn, relu=True, pool=pool, hw=(hw, hw),
+                                            cin_pad=IN_CHANNELS_PADDED if first else None))
+                first = False
+                i += 4 if pool else 3
+                continue
             spec = ConvBNActSpec(conv, bn, relu=True, pool=pool,
                                  cin_pad=IN_CHANNELS_PADDED if first else None)
             # this block's dgrad produces the gradient at the previous block's output: it
@@ -86,13 +100,13 @@ class _VGG(nn.Module):
         return self.fused_plan() if self.fc1.weight.is_cuda else []
 
     def _features_fused(self, x):
-        from ..ops.layers import conv_bn_act, to_nhwc_input
+        from ..ops.layers import conv_block, to_nhwc_input
         from ..ops.common import step_scratch
         plan = self.fused_plan()
         step_scratch(x.device).zero()  # BN statistics / backward sums of every layer: one fill
         h = to_nhwc_input(x, IN_CHANNELS_PADDED)
         for spec in plan:
-            h = conv_bn_act(h, spec)
+            h = conv_block(h, spec)
         if h.shape[1] != 1 or h.shape[2] != 1:
             raise RuntimeError("VGG head expects 1x1 spatial features (32x32 input)")
         return h.view(h.shape[0], -1)  # NHWC with H=W=1: identical to the NCHW flatten
@@ -126,7 +140,7 @@ class _VGG(nn.Module):
         split[-1] (+ fc1) and ``h_k.backward(leaf_k.grad)`` for k = len-1 .. 0 those of each
         earlier segment — backward segments the DDP engine can put collectives between
         (engine/step.py SegmentedDDPStep). ``soft``: as in ``forward_loss``."""
-        from ..ops.layers import conv_bn_act, to_nhwc_input, linear_cross_entropy
+        from ..ops.layers import conv_block, to_nhwc_input, linear_cross_entropy
         from ..ops.common import step_scratch
         plan = self.fused_plan()
         splits = [split] if isinstance(split, int) else list(split)
@@ -137,14 +151,15 @@ class _VGG(nn.Module):
         cuts, prev = [], 0
         for sp in splits + [len(plan)]:
             for spec in plan[prev:sp]:
-                h = conv_bn_act(h, spec)
+                h = conv_block(h, spec)
             if sp < len(plan):
                 leaf = h.detach().requires_grad_(True)
                 cuts.append((h, leaf))
                 h = leaf
             prev = sp
         loss = linear_cross_entropy(h.view(h.shape[0], -1), self.fc1, labels, acc, transient,
-                                    bn_prev=plan[-1], soft=soft)
+                                    bn_prev=plan[-1] if self.norm == "batch" else None,
+                                    soft=soft)
         return loss, cuts
 
     def n_stages(self):
@@ -171,6 +186,9 @@ class _VGG(nn.Module):
                 acc.add_(loss.detach())
             return loss
         from ..ops.layers import HEAD_NARROW_MAX, linear_cross_entropy
+        if self.norm == "group":  # no BatchNorm to fold into the head: it reads stored features
+            return linear_cross_entropy(self._features_fused(x), self.fc1, labels, acc, transient,
+                                        bn_prev=None, soft=soft)
         last = self.fused_plan()[-1]
         # its BN + ReLU + pool may run inside the narrow head's kernel; the wide head (more than 16
         # classes) reads stored features, so the block then runs its own pass
@@ -182,17 +200,17 @@ class _VGG(nn.Module):
         return linear_cross_entropy(h, self.fc1, labels, acc, transient, bn_prev=last, soft=soft)
 
 
-def VGG11(num_classes=10):
-    return _VGG('VGG11', num_classes)
+def VGG11(num_classes=10, norm="batch", gn_groups=32):
+    return _VGG('VGG11', num_classes, norm, gn_groups)
 
 
-def VGG13(num_classes=10):
-    return _VGG('VGG13', num_classes)
+def VGG13(num_classes=10, norm="batch", gn_groups=32):
+    return _VGG('VGG13', num_classes, norm, gn_groups)
 
 
-def VGG16(num_classes=10):
-    return _VGG('VGG16', num_classes)
+def VGG16(num_classes=10, norm="batch", gn_groups=32):
+    return _VGG('VGG16', num_classes, norm, gn_groups)
 
 
-def VGG19(num_classes=10):
-    return _VGG('VGG19', num_classes)
+def VGG19(num_classes=10, norm="batch", gn_groups=32):
+    return _VGG('VGG19', num_classes, norm, gn_groups)

@@ -772,6 +772,83 @@ def conv_bn_act(x, spec, residual=None, in_link=None, res_link=None, res_bn=None
                               in_link, res_link, res_bn)
 
 
+# ------------------------------------------------------------------ Conv -> GroupNorm -> ReLU
+GN_RANGE = ("GroupNorm is served for a multiple of 8 channels, a power of two up to 64 channels "
+            "per group, even height and width under the 2x2 pool, and max(8, channels per group) "
+            "* height * width <= 8192")
+
+
+class ConvGNActSpec(ConvBNActSpec):
+    """Conv2d(+bias) -> GroupNorm -> ReLU (-> MaxPool 2x2): ``bn`` is an nn.GroupNorm. The conv
+    runs without a statistics epilogue, then one group_norm.hip launch normalises, activates and
+    pools from a tile it keeps in registers. Never chained (``prev`` / ``next`` stay None) and
+    none of the BatchNorm fusions apply. ``hw``: the conv output's (height, width) when known at
+    construction (the whole range is then checked here, else the channel rules only).
+    The parent constructor also reserves what only BatchNorm reads (the StepScratch statistics
+    and backward-sum replicas, the coefficient table): a few KB per layer that this path never
+    touches, zeroed with the rest by the model's one per-forward fill (no extra launch)."""
+
+    def __init__(self, conv, gn, relu=True, pool=False, cin_pad=None, hw=None):
+        if not isinstance(gn, torch.nn.GroupNorm) or not gn.affine:
+            raise ValueError("ConvGNActSpec takes an affine nn.GroupNorm")
+        super().__init__(conv, gn, relu=relu, pool=pool, cin_pad=cin_pad)
+        self.gn_groups = gn.num_groups
+        P, Q = hw if hw is not None else (2, 2)
+        if gn.num_channels != self.K or not native().gn_ok(1, P, Q, self.K, self.gn_groups,
+                                                           int(pool)):
+            raise ValueError(f"{GN_RANGE} (got {self.K} channels in {self.gn_groups} groups"
+                             + (f" on {P}x{Q}" if hw is not None else "") + ")")
+
+
+class _ConvGNActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, spec):
+        spec.maybe_pack()
+        N, H, W, _ = x.shape
+        z = conv_forward(spec, x, bias, None)  # no statistics epilogue, no statistics atomics
+        _, P, Q, K = z.shape
+        if not native().gn_ok(N, P, Q, K, spec.gn_groups, int(spec.pool)):
+            raise ValueError(f"{GN_RANGE} (got {K} channels in {spec.gn_groups} groups on "
+                             f"{P}x{Q})")
+        Ho, Wo = (P // 2, Q // 2) if spec.pool else (P, Q)
+        y = torch.empty(N, Ho, Wo, K, dtype=BF16, device=x.device)
+        table = torch.empty(N, spec.gn_groups, 2, dtype=F32, device=x.device)  # (mu, is)
+        native().gn_act_fwd(N, P, Q, K, spec.gn_groups, int(spec.pool), int(spec.relu), spec.eps,
+                            ptr(z), ptr(gamma), ptr(beta), ptr(y), ptr(table), stream_handle())
+        ctx.spec = spec
+        ctx.save_for_backward(x, z, table, weight, bias, gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        spec = ctx.spec
+        x, z, table, weight, bias, gamma, beta = ctx.saved_tensors
+        N, P, Q, K = z.shape
+        dy = dy.contiguous()
+        dz = torch.empty_like(z)
+        gw, gg, gbt = ensure_grad(weight), ensure_grad(gamma), ensure_grad(beta)
+        # the conv bias has a real gradient here: only the GROUP sum of dz vanishes
+        gb = ensure_grad(bias) if bias is not None else None
+        ws = workspace(x.device)
+        native().gn_act_bwd(N, P, Q, K, spec.gn_groups, int(spec.pool), int(spec.relu), spec.eps,
+                            ptr(z), ptr(gamma), ptr(beta), ptr(table), ptr(dy), ptr(dz), ptr(gg),
+                            ptr(gbt), ptr(gb), ptr(ws), ws.numel(), stream_handle())
+        grad_ready([gamma, beta, bias])
+        dx = conv_backward(spec, x, dz, gw, ctx.needs_input_grad[0], None, weight=weight)
+        return dx, None, None, None, None, None
+
+
+def conv_gn_act(x, spec):
+    """Fused conv -> GroupNorm -> ReLU (-> 2x2 pool) of a ConvGNActSpec."""
+    conv, gn = spec.conv, spec.bn
+    return _ConvGNActFn.apply(x, conv.weight, conv.bias, gn.weight, gn.bias, spec)
+
+
+def conv_block(x, spec):
+    """The block of ``spec`` by its type (models/vgg.py)."""
+    return conv_gn_act(x, spec) if isinstance(spec, ConvGNActSpec) else conv_bn_act(x, spec)
+
+
 # ------------------------------------------------------------------ classifier head
 class _LinearSmallFn(torch.autograd.Function):
     """Linear with few outputs (J <= 128; the wide MFMA head above 16): bf16 [B, F] -> fp32

@@ -45,6 +45,14 @@ def build_parser(description=None, distributed=True):
                         'head (100 = CIFAR-100); a VGG on the GPU serves up to 16 with the '
                         'one-wave-per-row head and 17..128 with the MFMA head (works inside '
                         '--graph); default 10')
+    g.add_argument('--norm', default='batch', choices=['batch', 'group'],
+                   help='normalisation layer of the model: batch (BatchNorm over the local '
+                        'batch, the reference) | group (GroupNorm: per-image statistics, the '
+                        'trained function does not depend on how the global batch is split; '
+                        'vgg11/13/16/19); default batch')
+    g.add_argument('--gn-groups', type=int, default=32,
+                   help='--norm group: groups per GroupNorm layer (channels per group a power '
+                        'of two up to 64); default 32')
     g.add_argument('--epochs', type=int, default=1)
     g.add_argument('--global-batch', type=int, default=256, help='split int(B/world) per rank')
     g.add_argument('--train-size', type=int, default=None, help='synthetic train-set size')
