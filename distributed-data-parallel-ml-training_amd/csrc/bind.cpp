@@ -265,6 +265,60 @@ PYBIND11_MODULE(_native, m) {
     a.ws = P<float>(ws); a.ws_elems = ws_elems;
     check(ddp_gn_act_bwd(&a, S(st)), "gn_act_bwd");
   });
+  // Squeeze-and-Excitation tail of a bottleneck (se.hip; api.h ddp_se_*): outside se_ok the
+  // launchers raise ValueError ("invalid arguments") and write nothing
+  m.def("se_ok", [](int N, int H, int W, int C, int reduction) {
+    return ddp_se_ok(N, H, W, C, reduction) != 0;
+  });
+  auto se_check = [](int rc, const char* what) {
+    if (rc < 0)
+      throw py::value_error(std::string(what) + " failed: invalid arguments (" +
+                            std::to_string(rc) + ")");
+    check(rc, what);
+  };
+  m.def("se_fwd", [se_check](int N, int H, int W, int C, int reduction, float eps, uintptr_t z,
+                             uintptr_t res, uintptr_t stats, uintptr_t gamma, uintptr_t beta,
+                             uintptr_t coef, uintptr_t w1, uintptr_t b1, uintptr_t w2,
+                             uintptr_t b2, uintptr_t S_, uintptr_t s, uintptr_t h, uintptr_t y,
+                             uintptr_t mask, uintptr_t ws, size_t ws_elems, uintptr_t st,
+                             uintptr_t running_mean, uintptr_t running_var, float momentum,
+                             int use_running) {
+    ddp_amd::SeArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.C = C; a.reduction = reduction; a.eps = eps;
+    a.momentum = momentum; a.use_running = use_running;
+    a.z = P<unsigned short>(z); a.res = P<unsigned short>(res); a.stats = P<float>(stats);
+    a.gamma = P<float>(gamma); a.beta = P<float>(beta); a.coef = P<float>(coef);
+    a.running_mean = P<float>(running_mean); a.running_var = P<float>(running_var);
+    a.w1 = P<float>(w1); a.b1 = P<float>(b1); a.w2 = P<float>(w2); a.b2 = P<float>(b2);
+    a.S = P<float>(S_); a.s = P<float>(s); a.h = P<float>(h);
+    a.y = P<unsigned short>(y); a.mask = P<unsigned char>(mask);
+    a.ws = P<float>(ws); a.ws_elems = ws_elems;
+    se_check(ddp_se_fwd(&a, S(st)), "se_fwd");
+  }, py::arg("N"), py::arg("P"), py::arg("Q"), py::arg("C"), py::arg("reduction"),
+     py::arg("eps"), py::arg("z"), py::arg("res"), py::arg("stats"), py::arg("gamma"),
+     py::arg("beta"), py::arg("coef"), py::arg("w1"), py::arg("b1"), py::arg("w2"),
+     py::arg("b2"), py::arg("S"), py::arg("s"), py::arg("h"), py::arg("y"), py::arg("mask"),
+     py::arg("ws"), py::arg("ws_elems"), py::arg("st"), py::arg("running_mean") = 0,
+     py::arg("running_var") = 0, py::arg("momentum") = 0.1f, py::arg("use_running") = 0);
+  m.def("se_bwd", [se_check](int N, int H, int W, int C, int reduction, uintptr_t z,
+                             uintptr_t dy, uintptr_t mask, uintptr_t coef, uintptr_t w1,
+                             uintptr_t w2, uintptr_t S_, uintptr_t s, uintptr_t h, uintptr_t G,
+                             uintptr_t dt2, uintptr_t dh, uintptr_t dm, uintptr_t dw1,
+                             uintptr_t db1, uintptr_t dw2, uintptr_t db2, uintptr_t dgamma,
+                             uintptr_t dbeta, uintptr_t dz, uintptr_t dres, uintptr_t ws,
+                             size_t ws_elems, uintptr_t st) {
+    ddp_amd::SeArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.C = C; a.reduction = reduction;
+    a.z = P<unsigned short>(z); a.dy = P<unsigned short>(dy); a.mask = P<unsigned char>(mask);
+    a.coef = P<float>(coef); a.w1 = P<float>(w1); a.w2 = P<float>(w2);
+    a.S = P<float>(S_); a.s = P<float>(s); a.h = P<float>(h); a.G = P<float>(G);
+    a.dt2 = P<float>(dt2); a.dh = P<float>(dh); a.dm = P<float>(dm);
+    a.dw1 = P<float>(dw1); a.db1 = P<float>(db1); a.dw2 = P<float>(dw2);
+    a.db2 = P<float>(db2); a.dgamma = P<float>(dgamma); a.dbeta = P<float>(dbeta);
+    a.dz = P<unsigned short>(dz); a.dres = P<unsigned short>(dres);
+    a.ws = P<float>(ws); a.ws_elems = ws_elems;
+    se_check(ddp_se_bwd(&a, S(st)), "se_bwd");
+  });
   // VGG input block with z recomputed (conv_l0.hip): forward = statistics + BN/ReLU/pool
   // passes into y; backward = BN-backward sums + dz passes (dgamma / dbeta accumulated)
   m.def("l0_ok", [](py::tuple g) {

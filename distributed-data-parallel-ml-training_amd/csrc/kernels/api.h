@@ -94,6 +94,48 @@ struct GnArgs {
   size_t ws_elems;
 };
 
+// Squeeze-and-Excitation tail of a bottleneck (se.hip): y = relu(bn3(z) * s[n,:] + res) with
+// s = sigmoid(W2 relu(W1 mean_hw(bn3(z)) + b1) + b2), forward and backward. The forward writes
+// the tables S, s, h and the mask; the backward reads them and the forward's coefficient table.
+struct SeArgs {
+  int N, P, Q, C;               // z shape
+  int reduction;                // Cr = C / reduction channels between the two linears
+  float eps, momentum;
+  int use_running;              // forward only: the table from the running statistics (eval)
+  const unsigned short* z;      // conv3 output (bf16)
+  const unsigned short* res;    // residual added before the ReLU (bf16, z's shape)
+  const float* stats;           // [kStatRep][2][C] from the conv epilogue
+  const float* gamma;           // [C]
+  const float* beta;
+  float* running_mean;          // optional, updated in the training forward
+  float* running_var;
+  float* coef;                  // [6][C] as BnArgs::coef
+  const float* w1;              // fc1 [Cr][C], fp32 masters
+  const float* b1;              // [Cr]
+  const float* w2;              // fc2 [C][Cr]
+  const float* b2;              // [C]
+  float* S;                     // [N][C] sum_hw z
+  float* s;                     // [N][C] the gate
+  float* h;                     // [N][Cr] relu(W1 m + b1)
+  unsigned short* y;            // forward output (bf16)
+  unsigned char* mask;          // [N*P*Q][C/8] ReLU mask bits (BnArgs::mask format)
+  const unsigned short* dy;     // backward: grad wrt y
+  float* G;                     // [2][N][C]: G1 = sum_hw dy*mask, G2 = sum_hw dy*mask*z
+  float* dt2;                   // [N][C] grad at the sigmoid's input
+  float* dh;                    // [N][Cr] grad at fc1's output (through the ReLU)
+  float* dm;                    // [N][C] grad at the pooled value
+  float* dw1;                   // grad arena slices (accumulated)
+  float* db1;
+  float* dw2;
+  float* db2;
+  float* dgamma;
+  float* dbeta;
+  unsigned short* dz;           // grad wrt z
+  unsigned short* dres;         // grad wrt the residual = dy * mask (optional)
+  float* ws;                    // fp32 partials of split pixel ranges (workspace)
+  size_t ws_elems;
+};
+
 // BatchNorm-backward statistics fused into a conv dgrad: the dgrad output IS the gradient at the
 // output of the preceding Conv->BN->ReLU(->2x2 max-pool) block, so its epilogue can accumulate
 // that block's backward sums S1 = sum dy_bn, S2 = sum dy_bn * xhat (recomputing the ReLU mask /
@@ -560,6 +602,15 @@ int ddp_dwconv_wgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, con
 int ddp_gn_ok(int N, int P, int Q, int C, int groups, int pool);
 int ddp_gn_act_fwd(const ddp_amd::GnArgs* a, hipStream_t st);
 int ddp_gn_act_bwd(const ddp_amd::GnArgs* a, hipStream_t st);
+// Squeeze-and-Excitation tail (se.hip). Served (ddp_se_ok = 1): C % 64 == 0, 64 <= C <= 2048,
+// C % reduction == 0, Cr = C / reduction a multiple of 16 in 16..128, any N, P, Q >= 1 (P * Q * C
+// and N * C below 2^31). 0 = launched; -1 = not served or a pointer missing, -2 = workspace too
+// small (nothing is written); > 0 = HIP error. fwd: finalize, squeeze, excite, apply; bwd (batch
+// statistics only): reduce, excite_bwd, param_bwd, apply_bwd; every parameter gradient += (no
+// float atomics anywhere)
+int ddp_se_ok(int N, int P, int Q, int C, int reduction);
+int ddp_se_fwd(const ddp_amd::SeArgs* a, hipStream_t st);
+int ddp_se_bwd(const ddp_amd::SeArgs* a, hipStream_t st);
 // classifier-head dx fused with the preceding block's whole BN backward + dW / db in one launch
 // (conv_igemm.hip linear_head_bwd_kernel): 1 launched, 0 not served, < 0 invalid, >= 2 HIP
 // error (rc - 2)

@@ -1,5 +1,6 @@
 """Model zoo: VGG-11/13/16/19 (reference family) ResNet-50 (driver's large-gradient config),
-ResNeXt-50 32x4d (the same module tree with a grouped conv2) and MobileNet v1 (depthwise-separable
+ResNeXt-50 32x4d (the same module tree with a grouped conv2), their Squeeze-and-Excitation
+variants and MobileNet v1 (depthwise-separable
 blocks)."""
 from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG  # noqa: F401
 
@@ -27,6 +28,14 @@ def build(name, num_classes=None, norm="batch", gn_groups=32):
     if name in ("resnext50_32x4d", "resnet50_32x4d"):
         from .resnet import resnext50_32x4d
         return resnext50_32x4d(**kw)
+    # the Squeeze-and-Excitation variants (csrc/kernels/se.hip); the "resnet..." spellings are
+    # aliases for the same reason
+    if name in ("se_resnet50", "resnet50_se"):
+        from .resnet import se_resnet50
+        return se_resnet50(**kw)
+    if name in ("se_resnext50_32x4d", "resnet50_32x4d_se"):
+        from .resnet import se_resnext50_32x4d
+        return se_resnext50_32x4d(**kw)
     if name in ("mobilenet_v1", "mobilenet"):
         from .mobilenet import mobilenet_v1
         return mobilenet_v1(**kw)

@@ -20,10 +20,27 @@ import torch.nn as nn
 STEM_POOL_FUSE = True
 
 
+class SEGate(nn.Module):
+    """Squeeze-and-Excitation gate (Hu et al. 2018): s = sigmoid(fc2(relu(fc1(mean_hw(u))))).
+    ``nn.Linear``, not a 1x1 ``Conv2d``: the optimizers (Muon) and the conv operand re-pack see a
+    plain 2-D tensor. The GPU path reads both weights as they are (csrc/kernels/se.hip)."""
+
+    def __init__(self, channels, reduction):
+        super().__init__()
+        self.reduction = reduction
+        self.fc1 = nn.Linear(channels, channels // reduction)
+        self.fc2 = nn.Linear(channels // reduction, channels)
+
+    def forward(self, u):  # CPU / ATen path, NCHW: the gated u
+        s = torch.sigmoid(self.fc2(torch.relu(self.fc1(u.mean((2, 3))))))
+        return u * s[:, :, None, None]
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64,
+                 se_reduction=None):
         super().__init__()
         # ResNeXt (torchvision's rule): conv2 is grouped over a wider bottleneck; its GPU path
         # is the grouped 3x3 kernel (csrc/kernels/conv_group.hip)
@@ -35,6 +52,10 @@ class Bottleneck(nn.Module):
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * self.expansion, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        # SE variant: bn3's output times a per-(image, channel) gate before the residual add
+        # (state keys se.fc1.* / se.fc2.*; every other key stays torchvision's)
+        if se_reduction is not None:
+            self.se = SEGate(planes * self.expansion, se_reduction)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -45,6 +66,8 @@ class Bottleneck(nn.Module):
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
+        if hasattr(self, "se"):
+            out = self.se(out)
         if self.downsample is not None:
             identity = self.downsample(x)
         return self.relu(out + identity)
@@ -61,6 +84,12 @@ class Bottleneck(nn.Module):
             # conv2's / conv3's dgrad produce the gradient at bn1's / bn2's output: their
             # epilogues accumulate those BatchNorms' backward sums (ops/layers.py BnBwdFuse)
             s2.prev, s3.prev = s1, s2
+            self._se = None
+            if hasattr(self, "se"):
+                # the SE tail (se.hip) has its own backward: bn2's sums are not offered to it
+                from ..ops.layers import SESpec
+                s3.prev = None
+                self._se = SESpec(self.se.fc1, self.se.fc2, self.se.reduction)
             self._specs = (s1, s2, s3, ds)
         return self._specs
 
@@ -72,6 +101,12 @@ class Bottleneck(nn.Module):
         link = GradLink() if (h.requires_grad and torch.is_grad_enabled()) else None
         out = conv_bn_act(h, s1, in_link=link)
         out = conv_bn_act(out, s2)
+        if self._se is not None:
+            # no shortcut fold: a projection's BatchNorm runs as its own block
+            from ..ops.layers import conv_bn_se_act
+            if sd is not None:
+                return conv_bn_se_act(out, s3, self._se, conv_bn_act(h, sd, in_link=link))
+            return conv_bn_se_act(out, s3, self._se, h, res_link=link)
         if sd is not None:
             if res_bn_fuse_ok(s3):
                 # the shortcut's BatchNorm runs inside bn3's passes (ops/layers.py RES_BN_FUSE)
@@ -84,10 +119,11 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes=1000, zero_init_residual=False,
-                 groups=1, width_per_group=64):
+                 groups=1, width_per_group=64, se_reduction=None):
         super().__init__()
         self.inplanes = 64
         self.groups, self.base_width = groups, width_per_group
+        self.se_reduction = se_reduction
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -117,7 +153,7 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(
                 nn.Conv2d(self.inplanes, planes * Bottleneck.expansion, 1, stride=stride, bias=False),
                 nn.BatchNorm2d(planes * Bottleneck.expansion))
-        kw = dict(groups=self.groups, base_width=self.base_width)
+        kw = dict(groups=self.groups, base_width=self.base_width, se_reduction=self.se_reduction)
         layers = [Bottleneck(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * Bottleneck.expansion
         for _ in range(1, blocks):
@@ -230,3 +266,13 @@ def resnet50(num_classes=1000):
 def resnext50_32x4d(num_classes=1000):
     """ResNeXt-50 32x4d (torchvision's keys and shapes): 25 028 904 parameters."""
     return ResNet((3, 4, 6, 3), num_classes, groups=32, width_per_group=4)
+
+
+def se_resnet50(num_classes=1000):
+    """SE-ResNet-50, reduction 16: 28 088 024 parameters (2 530 992 in the gates)."""
+    return ResNet((3, 4, 6, 3), num_classes, se_reduction=16)
+
+
+def se_resnext50_32x4d(num_classes=1000):
+    """SE-ResNeXt-50 32x4d, reduction 16: 27 559 896 parameters."""
+    return ResNet((3, 4, 6, 3), num_classes, groups=32, width_per_group=4, se_reduction=16)

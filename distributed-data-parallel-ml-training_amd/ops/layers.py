@@ -772,8 +772,119 @@ def conv_bn_act(x, spec, residual=None, in_link=None, res_link=None, res_bn=None
                               in_link, res_link, res_bn)
 
 
+# ------------------------------------------------------------------ Conv -> BN -> SE gate -> ReLU
+SE_RANGE = ("Squeeze-and-Excitation is served for 64 to 2048 channels in multiples of 64 with "
+            "channels / reduction a multiple of 16 between 16 and 128")
+
+
+class SESpec:
+    """The gate of an SE bottleneck: ``fc1`` = nn.Linear(C, C // reduction), ``fc2`` =
+    nn.Linear(C // reduction, C), both read by se.hip as fp32 masters (no packed copy)."""
+
+    def __init__(self, fc1, fc2, reduction):
+        C = fc2.out_features
+        shapes_ok = (fc1.in_features == C and reduction >= 1 and C % reduction == 0
+                     and fc1.out_features == fc2.in_features == C // reduction
+                     and fc1.bias is not None and fc2.bias is not None)
+        if not shapes_ok or not native().se_ok(1, 1, 1, C, int(reduction)):
+            raise ValueError(f"{SE_RANGE} (got {C} channels, reduction {reduction})")
+        self.fc1, self.fc2, self.C, self.reduction = fc1, fc2, C, int(reduction)
+        self.Cr = C // self.reduction
+
+    def params(self):
+        return [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
+
+
+class _ConvBNSEActFn(torch.autograd.Function):
+    """conv3 -> bn3 -> per-image channel gate -> + residual -> ReLU (se.hip): the conv with its
+    statistics epilogue, then finalize / squeeze / excite / apply; the backward is reduce /
+    excite_bwd / param_bwd / apply_bwd and the conv's. None of the BatchNorm fusions apply."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, w1, b1, w2, b2, residual, spec, se,
+                in_link=None, res_link=None):
+        spec.maybe_pack()
+        spec.dz_fused = None
+        spec.deferred = None
+        if spec.prev is not None or spec.pool or not spec.relu or spec.maxpool3:
+            raise ValueError("the SE tail takes an unchained residual block without a pool")
+        z = conv_forward(spec, x, bias, spec.stats)
+        spec.fwd_z = None
+        N, P, Q, K = z.shape
+        if K != se.C or not native().se_ok(N, P, Q, K, se.reduction):
+            raise ValueError(f"{SE_RANGE} (got {K} channels, reduction {se.reduction})")
+        check(residual, BF16, (N, P, Q, K), "residual")
+        bn = spec.bn
+        rm = rv = None
+        use_running = 0
+        if bn.track_running_stats and bn.running_mean is not None:
+            rm, rv = bn.running_mean, bn.running_var
+            use_running = 0 if bn.training else 1
+        dev = x.device
+        y = torch.empty_like(z)
+        mask = torch.empty(N, P, Q, K // 8, dtype=torch.uint8, device=dev)
+        S = torch.empty(N, K, dtype=F32, device=dev)
+        s = torch.empty(N, K, dtype=F32, device=dev)
+        h = torch.empty(N, se.Cr, dtype=F32, device=dev)
+        ws = workspace(dev)
+        native().se_fwd(N, P, Q, K, se.reduction, spec.eps, ptr(z), ptr(residual),
+                        ptr(spec.stats), ptr(gamma), ptr(beta), ptr(spec.coef), ptr(w1), ptr(b1),
+                        ptr(w2), ptr(b2), ptr(S), ptr(s), ptr(h), ptr(y), ptr(mask), ptr(ws),
+                        ws.numel(), stream_handle(), running_mean=ptr(rm), running_var=ptr(rv),
+                        momentum=float(bn.momentum if bn.momentum is not None else 0.1),
+                        use_running=use_running)
+        ctx.spec, ctx.se, ctx.in_link, ctx.res_link = spec, se, in_link, res_link
+        ctx.save_for_backward(x, z, S, s, h, mask, weight, bias, gamma, beta, w1, b1, w2, b2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        spec, se = ctx.spec, ctx.se
+        x, z, S, s, h, mask, weight, bias, gamma, beta, w1, b1, w2, b2 = ctx.saved_tensors
+        N, P, Q, K = z.shape
+        dev = z.device
+        dy = dy.contiguous()
+        link = ctx.res_link
+        # the residual gradient is exactly dy through the mask: an identity block leaves it to
+        # the branch's first conv (GradLink.defer), as the plain block does
+        defer = (RES_DEFER and link is not None and ctx.needs_input_grad[9] and link.seen == 0
+                 and link.buf is None)
+        dres = torch.empty_like(z) if ctx.needs_input_grad[9] and not defer else None
+        dz = torch.empty_like(z)
+        G = torch.empty(2, N, K, dtype=F32, device=dev)
+        dt2 = torch.empty(N, K, dtype=F32, device=dev)
+        dh = torch.empty(N, se.Cr, dtype=F32, device=dev)
+        dm = torch.empty(N, K, dtype=F32, device=dev)
+        gw = ensure_grad(weight)
+        if bias is not None:
+            ensure_grad(bias)  # analytically zero under batch-statistics BN (bn_act.hip)
+        ws = workspace(dev)
+        native().se_bwd(N, P, Q, K, se.reduction, ptr(z), ptr(dy), ptr(mask), ptr(spec.coef),
+                        ptr(w1), ptr(w2), ptr(S), ptr(s), ptr(h), ptr(G), ptr(dt2), ptr(dh),
+                        ptr(dm), ptr(ensure_grad(w1)), ptr(ensure_grad(b1)),
+                        ptr(ensure_grad(w2)), ptr(ensure_grad(b2)), ptr(ensure_grad(gamma)),
+                        ptr(ensure_grad(beta)), ptr(dz), ptr(dres), ptr(ws), ws.numel(),
+                        stream_handle())
+        grad_ready([gamma, beta, bias, w1, b1, w2, b2])
+        if defer:
+            dres = link.defer(dy, mask)
+        elif link is not None and dres is not None:
+            dres = link.offer(dres)
+        dx = conv_backward(spec, x, dz, gw, ctx.needs_input_grad[0], ctx.in_link, weight=weight)
+        return (dx,) + (None,) * 8 + (dres, None, None, None, None)
+
+
+def conv_bn_se_act(x, spec3, se, residual, in_link=None, res_link=None):
+    """Fused conv -> BN -> SE gate -> + residual -> ReLU of an SE bottleneck's tail: ``spec3``
+    the conv3 / bn3 ConvBNActSpec (``prev`` None), ``se`` its SESpec."""
+    conv, bn = spec3.conv, spec3.bn
+    return _ConvBNSEActFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, se.fc1.weight,
+                                se.fc1.bias, se.fc2.weight, se.fc2.bias, residual, spec3, se,
+                                in_link, res_link)
+
+
 # ------------------------------------------------------------------ Conv -> GroupNorm -> ReLU
-GN_RANGE = ("GroupNorm is served for a multiple of 8 channels, a power of two up to 64 channels "
+GN_RANGE =("GroupNorm is served for a multiple of 8 channels, a power of two up to 64 channels "
             "per group, even height and width under the 2x2 pool, and max(8, channels per group) "
             "* height * width <= 8192")
 
