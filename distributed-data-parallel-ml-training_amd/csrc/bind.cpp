@@ -265,6 +265,35 @@ PYBIND11_MODULE(_native, m) {
     a.ws = P<float>(ws); a.ws_elems = ws_elems;
     check(ddp_gn_act_bwd(&a, S(st)), "gn_act_bwd");
   });
+  // Ghost BatchNorm + ReLU (+ pool) on fixed-size image groups (ghost_bn.hip; api.h ddp_gbn_*):
+  // outside gbn_ok the launchers raise "invalid arguments" and write nothing
+  m.def("gbn_ok", [](int N, int H, int W, int C, int ghost, int pool, size_t ws_elems) {
+    return ddp_gbn_ok(N, H, W, C, ghost, pool, ws_elems) != 0;
+  });
+  m.def("gbn_act_fwd", [](int N, int H, int W, int C, int ghost, int pool, int relu, float eps,
+                          uintptr_t z, uintptr_t gamma, uintptr_t beta, uintptr_t y,
+                          uintptr_t table, uintptr_t ws, size_t ws_elems, uintptr_t st) {
+    ddp_amd::GhostBnArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.C = C; a.ghost = ghost; a.pool = pool; a.relu = relu;
+    a.eps = eps;
+    a.z = P<unsigned short>(z); a.gamma = P<float>(gamma); a.beta = P<float>(beta);
+    a.y = P<unsigned short>(y); a.table = P<float>(table);
+    a.ws = P<float>(ws); a.ws_elems = ws_elems;
+    check(ddp_gbn_act_fwd(&a, S(st)), "gbn_act_fwd");
+  });
+  m.def("gbn_act_bwd", [](int N, int H, int W, int C, int ghost, int pool, int relu, float eps,
+                          uintptr_t z, uintptr_t gamma, uintptr_t beta, uintptr_t table,
+                          uintptr_t dy, uintptr_t dz, uintptr_t dgamma, uintptr_t dbeta,
+                          uintptr_t ws, size_t ws_elems, uintptr_t st) {
+    ddp_amd::GhostBnArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.C = C; a.ghost = ghost; a.pool = pool; a.relu = relu;
+    a.eps = eps;
+    a.z = P<unsigned short>(z); a.gamma = P<float>(gamma); a.beta = P<float>(beta);
+    a.table = P<float>(table); a.dy = P<unsigned short>(dy); a.dz = P<unsigned short>(dz);
+    a.dgamma = P<float>(dgamma); a.dbeta = P<float>(dbeta);
+    a.ws = P<float>(ws); a.ws_elems = ws_elems;
+    check(ddp_gbn_act_bwd(&a, S(st)), "gbn_act_bwd");
+  });
   // Squeeze-and-Excitation tail of a bottleneck (se.hip; api.h ddp_se_*): outside se_ok the
   // launchers raise ValueError ("invalid arguments") and write nothing
   m.def("se_ok", [](int N, int H, int W, int C, int reduction) {

@@ -94,6 +94,28 @@ struct GnArgs {
   size_t ws_elems;
 };
 
+// Ghost BatchNorm + ReLU (+ 2x2 max-pool) on fixed-size image groups (ghost_bn.hip): image n of
+// the batch belongs to group n % ngroups, ngroups = ceil(N / ghost); statistics per (group,
+// channel). No running statistics: eval runs the same forward.
+struct GhostBnArgs {
+  int N, P, Q, C;               // z / pre-pool shape
+  int ghost;                    // images per group (the last groups hold one fewer on a tail batch)
+  int pool;                     // 0: none, 1: 2x2 stride-2 max-pool
+  int relu;                     // apply ReLU
+  float eps;
+  const unsigned short* z;      // conv output (bf16)
+  const float* gamma;           // [C]
+  const float* beta;            // [C]
+  unsigned short* y;            // forward output (bf16, pooled shape)
+  float* table;                 // [ngroups][2][C] (mu, is): the forward writes, the backward reads
+  const unsigned short* dy;     // backward: grad wrt the block output (pooled shape)
+  unsigned short* dz;           // backward: grad wrt the conv output
+  float* dgamma;                // grad arena slices (accumulated)
+  float* dbeta;
+  float* ws;                    // fp32 partials [work item][2][8 CL] of either direction
+  size_t ws_elems;
+};
+
 // Squeeze-and-Excitation tail of a bottleneck (se.hip): y = relu(bn3(z) * s[n,:] + res) with
 // s = sigmoid(W2 relu(W1 mean_hw(bn3(z)) + b1) + b2), forward and backward. The forward writes
 // the tables S, s, h and the mask; the backward reads them and the forward's coefficient table.
@@ -602,6 +624,16 @@ int ddp_dwconv_wgrad(const ddp_amd::ConvGeom* g, int groups, const void* dz, con
 int ddp_gn_ok(int N, int P, int Q, int C, int groups, int pool);
 int ddp_gn_act_fwd(const ddp_amd::GnArgs* a, hipStream_t st);
 int ddp_gn_act_bwd(const ddp_amd::GnArgs* a, hipStream_t st);
+// Ghost BatchNorm + ReLU (+ pool) (ghost_bn.hip). Served (ddp_gbn_ok = 1): C % 8 == 0, N >= 1,
+// ghost >= 1, even P and Q with the pool, tensors below 2^31 elements, and the partials
+// (ddp_gbn_ws_elems floats) fit ``ws_elems``. 0 = launched; -1 = not served or a null pointer
+// (nothing is written); > 0 = HIP error. fwd: stats + apply launches, the (mu, is) table written;
+// bwd: reduce + apply launches, dz written whole, dgamma / dbeta += over groups then chunks in a
+// fixed order (no float atomics). Both directions use ``ws``.
+int ddp_gbn_ok(int N, int P, int Q, int C, int ghost, int pool, size_t ws_elems);
+size_t ddp_gbn_ws_elems(int N, int P, int Q, int C, int ghost, int pool);
+int ddp_gbn_act_fwd(const ddp_amd::GhostBnArgs* a, hipStream_t st);
+int ddp_gbn_act_bwd(const ddp_amd::GhostBnArgs* a, hipStream_t st);
 // Squeeze-and-Excitation tail (se.hip). Served (ddp_se_ok = 1): C % 64 == 0, 64 <= C <= 2048,
 // C % reduction == 0, Cr = C / reduction a multiple of 16 in 16..128, any N, P, Q >= 1 (P * Q * C
 // and N * C below 2^31). 0 = launched; -1 = not served or a pointer missing, -2 = workspace too

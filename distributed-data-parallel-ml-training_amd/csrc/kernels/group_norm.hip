@@ -58,11 +58,14 @@
 // would need a streaming variant.
 #include "common.h"
 #include "api.h"
+#include "norm_tile.h"
 
 #include <algorithm>
 
 namespace ddp_amd {
 namespace gn {
+
+using namespace tile;  // F8, cvt8, pack8, ldf8, xhat_of, pre_of
 
 constexpr int kBudget = 8192;  // resident elements of one slab unit: 4 vectors x 8 x 256 lanes
 constexpr int kFold = 16;      // slots added by one lane in the first LDS phase
@@ -72,29 +75,6 @@ struct Plan {
   float inv_m;                     // 1 / (Cg * P * Q)
   FastDiv dCL, dWo, dSlab;
 };
-
-struct F8 { float v[8]; };
-
-__device__ __forceinline__ F8 cvt8(uint4 u) {
-  F8 r;
-  r.v[0] = __uint_as_float(u.x << 16); r.v[1] = __uint_as_float(u.x & 0xffff0000u);
-  r.v[2] = __uint_as_float(u.y << 16); r.v[3] = __uint_as_float(u.y & 0xffff0000u);
-  r.v[4] = __uint_as_float(u.z << 16); r.v[5] = __uint_as_float(u.z & 0xffff0000u);
-  r.v[6] = __uint_as_float(u.w << 16); r.v[7] = __uint_as_float(u.w & 0xffff0000u);
-  return r;
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 u;
-  u.x = (unsigned)f2bf(f[0]) | ((unsigned)f2bf(f[1]) << 16);
-  u.y = (unsigned)f2bf(f[2]) | ((unsigned)f2bf(f[3]) << 16);
-  u.z = (unsigned)f2bf(f[4]) | ((unsigned)f2bf(f[5]) << 16);
-  u.w = (unsigned)f2bf(f[6]) | ((unsigned)f2bf(f[7]) << 16);
-  return u;
-}
-__device__ __forceinline__ F8 ldf8(const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  return F8{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
 
 // This thread's place in the tile. Idle lanes (past the last whole slot, when CL does not divide
 // 256) take slot = nslots, chunk lane 0: they add zeros, read live cells and write nothing.
@@ -182,10 +162,6 @@ __device__ __forceinline__ void group_sum(float (&v)[NV], float* lds, const Lane
   }
   slot_sum<NV>(v, lds, l, p);
 }
-
-// xhat and the pre-activation: ONE expression for the forward and the backward's recompute
-__device__ __forceinline__ float xhat_of(float z, float mu, float is) { return (z - mu) * is; }
-__device__ __forceinline__ float pre_of(float xh, float g, float b) { return __builtin_fmaf(xh, g, b); }
 
 // the tile's z as fp32 (zeros outside the image)
 __device__ __forceinline__ void load_tile(const unsigned short* base, const Lane& l, int C,

@@ -58,8 +58,8 @@ def main(part, argv=None):
                                mixup_alpha=args.mixup_alpha)  # --mixup-alpha
     test_loader = make_loader(test_ds, batch_size, device, train=False, shard=False)
 
-    model = build(args.model, None if nc == 10 else nc, norm=args.norm,  # --norm, --gn-groups
-                  gn_groups=args.gn_groups).to(device)
+    model = build(args.model, None if nc == 10 else nc, norm=args.norm,  # --norm, --gn-groups,
+                  gn_groups=args.gn_groups, ghost_batch=args.ghost_batch).to(device)  # --ghost-batch
     comm = make_communicator(device) if distributed else None
     if strategy == "ddp":
         # --graph on a GPU captures the step (TrainStep: inline collectives, one bucket is

@@ -2,18 +2,23 @@
 ResNeXt-50 32x4d (the same module tree with a grouped conv2), their Squeeze-and-Excitation
 variants and MobileNet v1 (depthwise-separable
 blocks)."""
-from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG  # noqa: F401
+from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG, GhostBatchNorm2d  # noqa: F401
 
 
-def build(name, num_classes=None, norm="batch", gn_groups=32):
+def build(name, num_classes=None, norm="batch", gn_groups=32, ghost_batch=32):
     """``num_classes``: the head's output count; None = the model's default. ``norm``: "batch"
-    (BatchNorm over the local batch) or "group" (GroupNorm with ``gn_groups`` groups: per-image
-    statistics; the VGG family)."""
+    (BatchNorm over the local batch), "group" (GroupNorm with ``gn_groups`` groups: per-image
+    statistics; the VGG family) or "ghost" (BatchNorm over interleaved groups of ``ghost_batch``
+    images: the same function for every per-GPU batch share; the VGG family)."""
     name = name.lower()
     kw = {} if num_classes is None else {"num_classes": int(num_classes)}
     table = {"vgg11": VGG11, "vgg13": VGG13, "vgg16": VGG16, "vgg19": VGG19}
-    if norm not in ("batch", "group"):
+    if norm not in ("batch", "group", "ghost"):
         raise ValueError(f"unknown norm {norm}")
+    if norm == "ghost":
+        if name not in table:
+            raise ValueError("--norm ghost is served for vgg11/13/16/19")
+        return table[name](norm="ghost", ghost_batch=int(ghost_batch), **kw)
     if norm == "group":
         if name not in table:
             raise ValueError("--norm group is served for vgg11/13/16/19")

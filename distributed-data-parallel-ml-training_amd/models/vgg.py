@@ -28,10 +28,37 @@ _cfg = {
 IN_CHANNELS_PADDED = 8  # first conv consumes 3 real + 5 zero channels on the MFMA path
 
 
-def _make_layers(cfg, norm="batch", gn_groups=32):
+class GhostBatchNorm2d(nn.BatchNorm2d):
+    """BatchNorm over fixed-size groups of ``ghost_batch`` images (Hoffer et al. 2017), without
+    running statistics. The groups are interleaved as the sharded sampler deals the samples:
+    with ngroups = ceil(N / ghost_batch), image n belongs to group n % ngroups, so the sets of
+    images that share statistics are the same for every world size that divides N / ghost_batch.
+    Parameter names and shapes are BatchNorm2d's; one group is the plain BatchNorm call. This
+    forward is the CPU path (and the oracle); GPU tensors run csrc/kernels/ghost_bn.hip."""
+
+    def __init__(self, num_features, ghost_batch=32, eps=1e-5):
+        super().__init__(num_features, eps=eps, track_running_stats=False)
+        if int(ghost_batch) < 1:
+            raise ValueError("ghost_batch must be a positive integer")
+        self.ghost_batch = int(ghost_batch)
+
+    def forward(self, x):
+        ngroups = -(-x.shape[0] // self.ghost_batch)
+        if ngroups <= 1:
+            return super().forward(x)
+        y = torch.empty_like(x)
+        for g in range(ngroups):
+            y[g::ngroups] = super().forward(x[g::ngroups])
+        return y
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, ghost_batch={self.ghost_batch}"
+
+
+def _make_layers(cfg, norm="batch", gn_groups=32, ghost_batch=32):
     """Same module sequence (and therefore the same Sequential indices) as part1/model.py:11-27.
     ``norm="group"``: nn.GroupNorm(gn_groups, v) where the BatchNorm sits (the same parameter
-    names and shapes)."""
+    names and shapes); ``norm="ghost"``: GhostBatchNorm2d(v, ghost_batch) there."""
     mods = []
     cin = 3
     for v in cfg:
@@ -40,6 +67,7 @@ def _make_layers(cfg, norm="batch", gn_groups=32):
             continue
         mods += [nn.Conv2d(cin, v, kernel_size=3, stride=1, padding=1, bias=True),
                  (nn.GroupNorm(gn_groups, v) if norm == "group"
+                  else GhostBatchNorm2d(v, ghost_batch) if norm == "ghost"
                   else nn.BatchNorm2d(v, track_running_stats=False)),
                  nn.ReLU(inplace=True)]
         cin = v
@@ -49,20 +77,21 @@ def _make_layers(cfg, norm="batch", gn_groups=32):
 class _VGG(nn.Module):
     """VGG module for 3x32x32 input, ``num_classes`` classes (default 10)."""
 
-    def __init__(self, name, num_classes=10, norm="batch", gn_groups=32):
+    def __init__(self, name, num_classes=10, norm="batch", gn_groups=32, ghost_batch=32):
         super().__init__()
-        if norm not in ("batch", "group"):
+        if norm not in ("batch", "group", "ghost"):
             raise ValueError(f"unknown norm {norm}")
         self.name = name
         self.norm = norm
-        self.layers = _make_layers(_cfg[name], norm, gn_groups)
+        self.ghost_batch = int(ghost_batch) if norm == "ghost" else None
+        self.layers = _make_layers(_cfg[name], norm, gn_groups, ghost_batch)
         self.fc1 = nn.Linear(512, num_classes)
         self._plan = None
 
     # ------------------------------------------------------------ fused GPU plan
     def fused_plan(self):
         """Group the Sequential into ConvBNAct stages (built once per device)."""
-        from ..ops.layers import ConvBNActSpec, ConvGNActSpec
+        from ..ops.layers import ConvBNActSpec, ConvGNActSpec, ConvGhostBNActSpec
         dev = self.fc1.weight.device
         if self._plan is not None and self._plan[0] == dev:
             return self._plan[1]
@@ -80,6 +109,12 @@ class _VGG(nn.Module):
                 hw = 32 >> sum(isinstance(m, nn.MaxPool2d) for m in mods[:i])
                 stages.append(ConvGNActSpec(conv, bn, relu=True, pool=pool, hw=(hw, hw),
                                             cin_pad=IN_CHANNELS_PADDED if first else None))
+                first = False
+                i += 4 if pool else 3
+                continue
+            if isinstance(bn, GhostBatchNorm2d):  # never chained either
+                stages.append(ConvGhostBNActSpec(conv, bn, relu=True, pool=pool,
+                                                 cin_pad=IN_CHANNELS_PADDED if first else None))
                 first = False
                 i += 4 if pool else 3
                 continue
@@ -111,11 +146,24 @@ class _VGG(nn.Module):
             raise RuntimeError("VGG head expects 1x1 spatial features (32x32 input)")
         return h.view(h.shape[0], -1)  # NHWC with H=W=1: identical to the NCHW flatten
 
+    def _head_cpu(self, y):
+        """fc1 on the CPU. A ghost model applies it per ghost group, as its normalisation: ATen's
+        GEMM rounds a row differently in a 16-row and an 8-row product, and per group the rows of
+        a call are the same whatever the world size, so the logits are too. One group (and every
+        other norm) is the plain call."""
+        ngroups = -(-y.shape[0] // self.ghost_batch) if self.ghost_batch else 1
+        if ngroups <= 1:
+            return self.fc1(y)
+        out = y.new_empty(y.shape[0], self.fc1.out_features)
+        for g in range(ngroups):
+            out[g::ngroups] = self.fc1(y[g::ngroups].contiguous())
+        return out
+
     def forward(self, x):
         if not x.is_cuda:
             y = self.layers(x)
             y = y.view(y.size(0), -1)
-            return self.fc1(y)
+            return self._head_cpu(y)
         from ..ops.layers import linear_small
         return linear_small(self._features_fused(x), self.fc1)
 
@@ -186,7 +234,7 @@ class _VGG(nn.Module):
                 acc.add_(loss.detach())
             return loss
         from ..ops.layers import HEAD_NARROW_MAX, linear_cross_entropy
-        if self.norm == "group":  # no BatchNorm to fold into the head: it reads stored features
+        if self.norm != "batch":  # no BatchNorm to fold into the head: it reads stored features
             return linear_cross_entropy(self._features_fused(x), self.fc1, labels, acc, transient,
                                         bn_prev=None, soft=soft)
         last = self.fused_plan()[-1]
@@ -200,17 +248,17 @@ class _VGG(nn.Module):
         return linear_cross_entropy(h, self.fc1, labels, acc, transient, bn_prev=last, soft=soft)
 
 
-def VGG11(num_classes=10, norm="batch", gn_groups=32):
-    return _VGG('VGG11', num_classes, norm, gn_groups)
+def VGG11(num_classes=10, norm="batch", gn_groups=32, ghost_batch=32):
+    return _VGG('VGG11', num_classes, norm, gn_groups, ghost_batch)
 
 
-def VGG13(num_classes=10, norm="batch", gn_groups=32):
-    return _VGG('VGG13', num_classes, norm, gn_groups)
+def VGG13(num_classes=10, norm="batch", gn_groups=32, ghost_batch=32):
+    return _VGG('VGG13', num_classes, norm, gn_groups, ghost_batch)
 
 
-def VGG16(num_classes=10, norm="batch", gn_groups=32):
-    return _VGG('VGG16', num_classes, norm, gn_groups)
+def VGG16(num_classes=10, norm="batch", gn_groups=32, ghost_batch=32):
+    return _VGG('VGG16', num_classes, norm, gn_groups, ghost_batch)
 
 
-def VGG19(num_classes=10, norm="batch", gn_groups=32):
-    return _VGG('VGG19', num_classes, norm, gn_groups)
+def VGG19(num_classes=10, norm="batch", gn_groups=32, ghost_batch=32):
+    return _VGG('VGG19', num_classes, norm, gn_groups, ghost_batch)

@@ -955,9 +955,82 @@ def conv_gn_act(x, spec):
     return _ConvGNActFn.apply(x, conv.weight, conv.bias, gn.weight, gn.bias, spec)
 
 
+# ------------------------------------------------------------------ Conv -> Ghost BatchNorm -> ReLU
+GBN_RANGE = ("Ghost BatchNorm is served for a multiple of 8 channels, a batch and a ghost batch "
+             "of at least 1, even height and width under the 2x2 pool, tensors below 2^31 "
+             "elements and partials within the workspace")
+
+
+class ConvGhostBNActSpec(ConvBNActSpec):
+    """Conv2d(+bias) -> GhostBatchNorm2d -> ReLU (-> MaxPool 2x2): BatchNorm statistics over
+    groups of ``bn.ghost_batch`` images, image n in group n % ngroups (ghost_bn.hip). The conv
+    runs without a statistics epilogue; two launches each way form the per-group statistics and
+    apply them. Never chained (``prev`` / ``next`` stay None) and none of the BatchNorm fusions
+    apply. As ConvGNActSpec, the parent constructor's BatchNorm reservations stay unused."""
+
+    def __init__(self, conv, bn, relu=True, pool=False, cin_pad=None):
+        ghost = getattr(bn, "ghost_batch", None)
+        if ghost is None or not bn.affine or bn.track_running_stats:
+            raise ValueError("ConvGhostBNActSpec takes an affine GhostBatchNorm2d")
+        super().__init__(conv, bn, relu=relu, pool=pool, cin_pad=cin_pad)
+        self.ghost = int(ghost)
+        if bn.num_features != self.K or self.ghost < 1:
+            raise ValueError(f"{GBN_RANGE} (got {self.K} channels, ghost batch {self.ghost})")
+
+
+class _ConvGhostBNActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, spec):
+        spec.maybe_pack()
+        z = conv_forward(spec, x, bias, None)  # no statistics epilogue, no statistics atomics
+        N, P, Q, K = z.shape
+        ws = workspace(x.device)
+        if not native().gbn_ok(N, P, Q, K, spec.ghost, int(spec.pool), ws.numel()):
+            raise ValueError(f"{GBN_RANGE} (got {K} channels, batch {N}, ghost batch "
+                             f"{spec.ghost} on {P}x{Q}{', pooled' if spec.pool else ''})")
+        Ho, Wo = (P // 2, Q // 2) if spec.pool else (P, Q)
+        y = torch.empty(N, Ho, Wo, K, dtype=BF16, device=x.device)
+        ngroups = -(-N // spec.ghost)
+        table = torch.empty(ngroups, 2, K, dtype=F32, device=x.device)  # (mu, is)
+        native().gbn_act_fwd(N, P, Q, K, spec.ghost, int(spec.pool), int(spec.relu), spec.eps,
+                             ptr(z), ptr(gamma), ptr(beta), ptr(y), ptr(table), ptr(ws),
+                             ws.numel(), stream_handle())
+        ctx.spec = spec
+        ctx.save_for_backward(x, z, table, weight, bias, gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        spec = ctx.spec
+        x, z, table, weight, bias, gamma, beta = ctx.saved_tensors
+        N, P, Q, K = z.shape
+        dy = dy.contiguous()
+        dz = torch.empty_like(z)
+        gw, gg, gbt = ensure_grad(weight), ensure_grad(gamma), ensure_grad(beta)
+        if bias is not None:
+            ensure_grad(bias)  # analytically zero: dz sums to zero over every group
+        ws = workspace(x.device)
+        native().gbn_act_bwd(N, P, Q, K, spec.ghost, int(spec.pool), int(spec.relu), spec.eps,
+                             ptr(z), ptr(gamma), ptr(beta), ptr(table), ptr(dy), ptr(dz), ptr(gg),
+                             ptr(gbt), ptr(ws), ws.numel(), stream_handle())
+        grad_ready([gamma, beta, bias])
+        dx = conv_backward(spec, x, dz, gw, ctx.needs_input_grad[0], None, weight=weight)
+        return dx, None, None, None, None, None
+
+
+def conv_gbn_act(x, spec):
+    """Fused conv -> Ghost BatchNorm -> ReLU (-> 2x2 pool) of a ConvGhostBNActSpec."""
+    conv, bn = spec.conv, spec.bn
+    return _ConvGhostBNActFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, spec)
+
+
 def conv_block(x, spec):
     """The block of ``spec`` by its type (models/vgg.py)."""
-    return conv_gn_act(x, spec) if isinstance(spec, ConvGNActSpec) else conv_bn_act(x, spec)
+    if isinstance(spec, ConvGNActSpec):
+        return conv_gn_act(x, spec)
+    if isinstance(spec, ConvGhostBNActSpec):
+        return conv_gbn_act(x, spec)
+    return conv_bn_act(x, spec)
 
 
 # ------------------------------------------------------------------ classifier head

@@ -47,11 +47,15 @@ def build_parser(description=None, distributed=True):
                         'head (100 = CIFAR-100); a VGG on the GPU serves up to 16 with the '
                         'one-wave-per-row head and 17..128 with the MFMA head (works inside '
                         '--graph); default 10')
-    g.add_argument('--norm', default='batch', choices=['batch', 'group'],
+    g.add_argument('--norm', default='batch', choices=['batch', 'group', 'ghost'],
                    help='normalisation layer of the model: batch (BatchNorm over the local '
                         'batch, the reference) | group (GroupNorm: per-image statistics, the '
                         'trained function does not depend on how the global batch is split; '
-                        'vgg11/13/16/19); default batch')
+                        'vgg11/13/16/19) | ghost (BatchNorm over interleaved groups of '
+                        '--ghost-batch images: the same groups for every world size that '
+                        'divides batch / ghost-batch; vgg11/13/16/19); default batch')
+    g.add_argument('--ghost-batch', type=_ghost_batch, default=32,
+                   help='--norm ghost: images per statistics group; default 32')
     g.add_argument('--gn-groups', type=int, default=32,
                    help='--norm group: groups per GroupNorm layer (channels per group a power '
                         'of two up to 64); default 32')
@@ -148,6 +152,13 @@ def _num_classes(v):
     n = int(v)
     if n < 2:
         raise argparse.ArgumentTypeError("--num-classes must be >= 2")
+    return n
+
+
+def _ghost_batch(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError("--ghost-batch must be >= 1")
     return n
 
 
