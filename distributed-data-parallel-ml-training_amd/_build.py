@@ -55,7 +55,8 @@ VARIANTS = {"release": ("_native", "native", []),
 # without them; the older ones keep the flags they were tuned and tested with
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"linear_wide.hip": _NO_PK_F32, "muon.hip": _NO_PK_F32, "dwconv.hip": _NO_PK_F32,
-               "group_norm.hip": _NO_PK_F32, "se.hip": _NO_PK_F32, "ghost_bn.hip": _NO_PK_F32}
+               "group_norm.hip": _NO_PK_F32, "se.hip": _NO_PK_F32, "ghost_bn.hip": _NO_PK_F32,
+               "rep_bn.hip": _NO_PK_F32}
 
 
 def ext_path(variant="release"):

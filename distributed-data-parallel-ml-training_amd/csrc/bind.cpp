@@ -348,6 +348,46 @@ PYBIND11_MODULE(_native, m) {
     a.ws = P<float>(ws); a.ws_elems = ws_elems;
     se_check(ddp_se_bwd(&a, S(st)), "se_bwd");
   });
+  // RepVGG block normalisation (rep_bn.hip; api.h ddp_rep_bn_*): y = relu(bn3(z3) + bn1(z1)
+  // [+ bn0(x)]). ``branches``: 2 or 3 tuples (z, stats, gamma, beta, running_mean, running_var,
+  // momentum, eps, coef, dz, dgamma, dbeta) in that order of branches, unused pointers 0. Outside
+  // rep_bn_ok the launchers raise "invalid arguments" and write nothing
+  m.def("rep_bn_ok", [](int N, int H, int W, int K) { return ddp_rep_bn_ok(N, H, W, K) != 0; });
+  m.def("rep_bn_ws_elems", &ddp_rep_bn_ws_elems);
+  auto rep_args = [](int N, int H, int W, int K, py::list branches) {
+    ddp_amd::RepBnArgs a{};
+    a.N = N; a.P = H; a.Q = W; a.K = K;
+    a.nbr = (int)branches.size();
+    for (int b = 0; b < a.nbr && b < 3; ++b) {
+      auto t = branches[b].cast<py::tuple>();
+      ddp_amd::RepBranch& r = a.br[b];
+      r.z = P<unsigned short>(t[0].cast<uintptr_t>()); r.stats = P<float>(t[1].cast<uintptr_t>());
+      r.gamma = P<float>(t[2].cast<uintptr_t>()); r.beta = P<float>(t[3].cast<uintptr_t>());
+      r.running_mean = P<float>(t[4].cast<uintptr_t>());
+      r.running_var = P<float>(t[5].cast<uintptr_t>());
+      r.momentum = t[6].cast<float>(); r.eps = t[7].cast<float>();
+      r.coef = P<float>(t[8].cast<uintptr_t>()); r.dz = P<unsigned short>(t[9].cast<uintptr_t>());
+      r.dgamma = P<float>(t[10].cast<uintptr_t>()); r.dbeta = P<float>(t[11].cast<uintptr_t>());
+    }
+    return a;
+  };
+  m.def("rep_bn_fwd", [rep_args](int N, int H, int W, int K, py::list branches, uintptr_t y,
+                                 uintptr_t ostats, int use_running, uintptr_t st) {
+    auto a = rep_args(N, H, W, K, branches);
+    a.y = P<unsigned short>(y); a.ostats = P<float>(ostats); a.use_running = use_running;
+    check(ddp_rep_bn_fwd(&a, S(st)), "rep_bn_fwd");
+  });
+  m.def("rep_bn_bwd", [rep_args](int N, int H, int W, int K, py::list branches, uintptr_t dy,
+                                 uintptr_t y, uintptr_t ws, size_t ws_elems, uintptr_t st) {
+    auto a = rep_args(N, H, W, K, branches);
+    a.dy = P<unsigned short>(dy); a.y = P<unsigned short>(y);
+    a.ws = P<float>(ws); a.ws_elems = ws_elems;
+    check(ddp_rep_bn_bwd(&a, S(st)), "rep_bn_bwd");
+  });
+  m.def("rep_bn_stats", [](int N, int H, int W, int K, uintptr_t x, uintptr_t stats,
+                           uintptr_t st) {
+    check(ddp_rep_bn_stats(P<void>(x), N, H, W, K, P<float>(stats), S(st)), "rep_bn_stats");
+  });
   // VGG input block with z recomputed (conv_l0.hip): forward = statistics + BN/ReLU/pool
   // passes into y; backward = BN-backward sums + dz passes (dgamma / dbeta accumulated)
   m.def("l0_ok", [](py::tuple g) {

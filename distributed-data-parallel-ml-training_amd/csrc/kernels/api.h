@@ -158,6 +158,35 @@ struct SeArgs {
   size_t ws_elems;
 };
 
+// RepVGG training block (rep_bn.hip): y = relu(bn3(z3) + bn1(z1) [+ bn0(x)]) over M = N * P * Q
+// rows of K channels; every branch is a BatchNorm2d with running statistics.
+struct RepBranch {
+  const unsigned short* z;      // the branch's input (bf16): conv output, or the block input x
+  const float* stats;           // [kStatRep][2][K] sum, sumsq of z over the M rows
+  const float* gamma;           // [K]
+  const float* beta;
+  float* running_mean;          // optional; updated by the training forward, read in eval mode
+  float* running_var;
+  float momentum, eps;
+  float* coef;                  // [6][K] as BnArgs::coef: the forward writes rows 0-3, the
+                                // backward reads mean / invstd / scale and writes k1, k2
+  unsigned short* dz;           // backward: grad wrt z
+  float* dgamma;                // grad arena slices (accumulated)
+  float* dbeta;
+};
+struct RepBnArgs {
+  int N, P, Q, K;
+  int nbr;                      // 2: 3x3 and 1x1 branches, 3: + the identity branch (br[2])
+  int use_running;              // forward only: the tables from the running statistics (eval)
+  RepBranch br[3];
+  unsigned short* y;            // forward output (bf16); the backward reads it for the ReLU mask
+  float* ostats;                // optional [kStatRep][2][K], zeroed by the caller: += sum, sumsq
+                                // of the stored (rounded) y = the next block's identity statistics
+  const unsigned short* dy;     // backward: grad wrt y
+  float* ws;                    // backward: fp32 partials [row block][slab][4][8 CL]
+  size_t ws_elems;
+};
+
 // BatchNorm-backward statistics fused into a conv dgrad: the dgrad output IS the gradient at the
 // output of the preceding Conv->BN->ReLU(->2x2 max-pool) block, so its epilogue can accumulate
 // that block's backward sums S1 = sum dy_bn, S2 = sum dy_bn * xhat (recomputing the ReLU mask /
@@ -643,6 +672,18 @@ int ddp_gbn_act_bwd(const ddp_amd::GhostBnArgs* a, hipStream_t st);
 int ddp_se_ok(int N, int P, int Q, int C, int reduction);
 int ddp_se_fwd(const ddp_amd::SeArgs* a, hipStream_t st);
 int ddp_se_bwd(const ddp_amd::SeArgs* a, hipStream_t st);
+// RepVGG block normalisation (rep_bn.hip). Served (ddp_rep_bn_ok = 1): K % 8 == 0, N, P, Q >= 1,
+// N * P * Q * K below 2^31. 0 = launched; -1 = not served, nbr outside 2..3 or a pointer missing,
+// -2 = workspace below ddp_rep_bn_ws_elems floats (nothing is written); > 0 = HIP error.
+// fwd: one launch (tables, running statistics, y, optional statistics of y); bwd (batch statistics
+// only): reduce + apply launches, every dz written whole, dgamma / dbeta += through partials added
+// in a fixed order (no float atomics). stats: clears ``stats`` ([kStatRep][2][K]) and accumulates
+// the sum / sumsq of x into it, for an identity branch whose producer did not.
+int ddp_rep_bn_ok(int N, int P, int Q, int K);
+size_t ddp_rep_bn_ws_elems(int N, int P, int Q, int K);
+int ddp_rep_bn_fwd(const ddp_amd::RepBnArgs* a, hipStream_t st);
+int ddp_rep_bn_bwd(const ddp_amd::RepBnArgs* a, hipStream_t st);
+int ddp_rep_bn_stats(const void* x, int N, int P, int Q, int K, float* stats, hipStream_t st);
 // classifier-head dx fused with the preceding block's whole BN backward + dW / db in one launch
 // (conv_igemm.hip linear_head_bwd_kernel): 1 launched, 0 not served, < 0 invalid, >= 2 HIP
 // error (rc - 2)

@@ -1,7 +1,7 @@
 """Model zoo: VGG-11/13/16/19 (reference family) ResNet-50 (driver's large-gradient config),
 ResNeXt-50 32x4d (the same module tree with a grouped conv2), their Squeeze-and-Excitation
-variants and MobileNet v1 (depthwise-separable
-blocks)."""
+variants, MobileNet v1 (depthwise-separable
+blocks) and RepVGG-A0 / A1 (three-branch BatchNorm blocks)."""
 from .vgg import VGG11, VGG13, VGG16, VGG19, _VGG, GhostBatchNorm2d  # noqa: F401
 
 
@@ -44,4 +44,8 @@ def build(name, num_classes=None, norm="batch", gn_groups=32, ghost_batch=32):
     if name in ("mobilenet_v1", "mobilenet"):
         from .mobilenet import mobilenet_v1
         return mobilenet_v1(**kw)
+    # RepVGG in training form (three-branch blocks, csrc/kernels/rep_bn.hip)
+    if name in ("repvgg_a0", "repvgg_a1"):
+        from .repvgg import repvgg
+        return repvgg(name, **kw)
     raise ValueError(f"unknown model {name}")

@@ -1033,6 +1033,128 @@ def conv_block(x, spec):
     return conv_bn_act(x, spec)
 
 
+# ------------------------------------------------------------------ RepVGG block
+REP_RANGE = ("the RepVGG block is served for a 3x3 / padding 1 and a 1x1 / padding 0 conv without "
+             "bias, of equal stride and a multiple of 8 output channels, BatchNorms with running "
+             "statistics, an identity BatchNorm only between equal shapes, and tensors below 2^31 "
+             "elements")
+
+
+class RepBlockSpec:
+    """RepVGG training block  y = relu(bn3(conv3(x)) + bn1(conv1(x)) [+ bn0(x)])  (rep_bn.hip).
+    ``s3`` / ``s1`` are ordinary ConvBNActSpecs (operand copies, statistics slots, packing hook)
+    whose BatchNorm passes never run on their own; the identity branch owns a statistics slot in
+    the per-step scratch and a coefficient table of its own. None of the BatchNorm fusions apply
+    and the specs are not chained."""
+
+    def __init__(self, conv3, bn3, conv1, bn1, bn0=None, cin_pad=None):
+        self.s3 = ConvBNActSpec(conv3, bn3, relu=False, cin_pad=cin_pad)
+        self.s1 = ConvBNActSpec(conv1, bn1, relu=False, cin_pad=cin_pad)
+        s3, s1 = self.s3, self.s1
+        bns = [bn3, bn1] + ([bn0] if bn0 is not None else [])
+        ok = ((s3.R, s3.S, s3.pad, s1.R, s1.S, s1.pad) == (3, 3, 1, 1, 1, 0)
+              and s3.stride == s1.stride and s3.K == s1.K and s3.Cr == s1.Cr
+              and s3.groups == s1.groups == 1 and conv3.bias is None and conv1.bias is None
+              and all(isinstance(b, torch.nn.BatchNorm2d) and b.affine and b.track_running_stats
+                      and b.num_features == s3.K for b in bns)
+              and (bn0 is None or (s3.Cr == s3.C == s3.K and s3.stride == 1)))
+        if not ok or not native().rep_bn_ok(1, 1, 1, s3.K):
+            raise ValueError(f"{REP_RANGE} (got {s3.Cr} -> {s3.K} channels, stride {s3.stride})")
+        self.K, self.bn0 = s3.K, bn0
+        self.stats0 = self.coef0 = None
+        if bn0 is not None:
+            n = stat_replicas() * 2 * self.K
+            self.stats0 = s3.scratch.take(n)[:n]
+            self.coef0 = torch.empty(6 * self.K, dtype=F32, device=conv3.weight.device)
+        # set by the producing block's forward: the tensor whose statistics stats0 holds
+        self.stats0_of = None
+
+    def branches(self):
+        out = [(self.s3.bn, self.s3.stats, self.s3.coef), (self.s1.bn, self.s1.stats, self.s1.coef)]
+        if self.bn0 is not None:
+            out.append((self.bn0, self.stats0, self.coef0))
+        return out
+
+    def native_branches(self, zs, dzs=None):
+        """The ``branches`` argument of rep_bn_fwd (dzs None) / rep_bn_bwd."""
+        out = []
+        for (bn, stats, coef), z, dz in zip(self.branches(), zs, dzs or (None,) * 3):
+            grads = (ensure_grad(bn.weight), ensure_grad(bn.bias)) if dz is not None else (None,) * 2
+            out.append((ptr(z), ptr(stats), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+                        ptr(bn.running_var), float(bn.momentum if bn.momentum is not None else 0.1),
+                        float(bn.eps), ptr(coef), ptr(dz), ptr(grads[0]), ptr(grads[1])))
+        return out
+
+
+class _RepBlockFn(torch.autograd.Function):
+    """Two plain conv forwards (statistics in their epilogues), then ONE rep_bn_fwd launch that
+    finalises the BatchNorms and writes y (and the next block's identity statistics); backward:
+    rep_bn_bwd (reduce + apply), then both convs' backwards onto one shared dx."""
+
+    @staticmethod
+    def forward(ctx, x, w3, g3, b3, w1, g1, b1, g0, b0, spec, next_spec):
+        s3, s1 = spec.s3, spec.s1
+        s3.maybe_pack()
+        s1.maybe_pack()
+        z3 = conv_forward(s3, x, None, s3.stats)
+        z1 = conv_forward(s1, x, None, s1.stats)
+        N, P, Q, K = z3.shape
+        nat, s = native(), stream_handle()
+        if not nat.rep_bn_ok(N, P, Q, K):
+            raise ValueError(f"{REP_RANGE} (got a {N} x {P} x {Q} x {K} output)")
+        training = s3.bn.training
+        have, spec.stats0_of = spec.stats0_of, None
+        if spec.bn0 is not None and training and have != x.data_ptr():
+            # the producer of x did not leave its statistics: the small statistics pass
+            nat.rep_bn_stats(N, P, Q, K, ptr(x), ptr(spec.stats0), s)
+        y = torch.empty_like(z3)
+        ostats = None
+        if next_spec is not None and next_spec.bn0 is not None and training:
+            ostats, next_spec.stats0_of = next_spec.stats0, y.data_ptr()
+        nat.rep_bn_fwd(N, P, Q, K, spec.native_branches((z3, z1, x)), ptr(y), ptr(ostats),
+                       int(not training), s)
+        ctx.spec = spec
+        ctx.save_for_backward(x, z3, z1, y, w3, w1)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        spec = ctx.spec
+        s3, s1 = spec.s3, spec.s1
+        x, z3, z1, y, w3, w1 = ctx.saved_tensors
+        if not s3.bn.training:
+            raise RuntimeError("the RepVGG block's backward needs batch statistics (train mode)")
+        N, P, Q, K = z3.shape
+        dy = dy.contiguous()
+        dz3, dz1 = torch.empty_like(z3), torch.empty_like(z1)
+        dx0 = torch.empty_like(x) if spec.bn0 is not None else None
+        ws = workspace(x.device)
+        native().rep_bn_bwd(N, P, Q, K, spec.native_branches((z3, z1, x), (dz3, dz1, dx0)),
+                            ptr(dy), ptr(y), ptr(ws), ws.numel(), stream_handle())
+        grad_ready([p for bn, _, _ in spec.branches() for p in (bn.weight, bn.bias)])
+        need = ctx.needs_input_grad[0]
+        link = None
+        if need:
+            # the identity gradient is already in the buffer both DGRADs accumulate into; without
+            # it the first DGRAD writes dx (a strided 1x1 leaves that to the 3x3, GradLink)
+            link = GradLink(3 if dx0 is not None else 2)
+            if dx0 is not None:
+                link.buf, link.seen = dx0, 1
+        conv_backward(s1, x, dz1, ensure_grad(w1), need, link, weight=w1)
+        dx = conv_backward(s3, x, dz3, ensure_grad(w3), need, link, weight=w3)
+        return (dx,) + (None,) * 10
+
+
+def rep_block(x, spec, next_spec=None):
+    """The RepVGG training block of a RepBlockSpec. ``next_spec``: the RepBlockSpec that consumes
+    the output; when it has an identity branch, this forward also leaves the statistics of y in
+    its slot, so that no block needs a statistics pass over its input."""
+    b3, b1, b0 = spec.s3.bn, spec.s1.bn, spec.bn0
+    return _RepBlockFn.apply(x, spec.s3.conv.weight, b3.weight, b3.bias, spec.s1.conv.weight,
+                             b1.weight, b1.bias, b0.weight if b0 is not None else None,
+                             b0.bias if b0 is not None else None, spec, next_spec)
+
+
 # ------------------------------------------------------------------ classifier head
 class _LinearSmallFn(torch.autograd.Function):
     """Linear with few outputs (J <= 128; the wide MFMA head above 16): bf16 [B, F] -> fp32

@@ -41,7 +41,8 @@ def build_parser(description=None, distributed=True):
     g.add_argument('--model', default='vgg11', help='vgg11 | vgg13 | vgg16 | vgg19 | resnet50 | resnext50_32x4d '
                         '(alias resnet50_32x4d) | se_resnet50 (alias resnet50_se) | '
                         'se_resnext50_32x4d (alias resnet50_32x4d_se) | mobilenet_v1 '
-                        '(alias mobilenet)')
+                        '(alias mobilenet) | repvgg_a0 | repvgg_a1 (training form, three-branch '
+                        'blocks)')
     g.add_argument('--num-classes', type=_num_classes, default=10,
                    help="classes of the synthetic CIFAR-shaped dataset and outputs of the model's "
                         'head (100 = CIFAR-100); a VGG on the GPU serves up to 16 with the '
